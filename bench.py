@@ -12,7 +12,14 @@ epochs are independent, so the path shards with no data-path collective ("weak")
 `--shard trials` instead splits ONE batch over the ranks (ShardedVAMP, exact-compat: the
 batch-global scalars of every iteration all-reduced through amp_set_allreduce_hook; "strong").
 
-  python bench.py [--gpus N --steps K --warmup W] [--shard epochs|trials]
+  python bench.py [--gpus N --steps K --warmup W] [--shard epochs|trials] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`, the error rates of the timed steps).  `--dump-outputs DIR` also writes what the
+last timed step returned as DIR/<name>.npy.  `--full` adds everything that takes runs of its own:
+the dominant kernel timed alone and inside a loop of forwards (`detail.kernel_ms`), the `roofline`
+block and the `cpu_baseline` (the numpy oracle on the host cores; `--no-cpu-baseline` leaves that
+one out).
 """
 import argparse
 import json
@@ -161,6 +168,44 @@ def timed_epochs(step, counts_of, steps, warmup, merge, sync=lambda: None, barri
     return max_over_ranks(el), merged, h, npre
 
 
+def dump_outputs(dirname, det, trials, rank):
+    """What the last timed step handed its caller, as float32 / float64 .npy files in `dirname`:
+    the detector state of that forward (r and xmmse as [B, N, 2] re/im pairs, var [B, N]; the
+    rank's rows under --shard trials) and its Loss (the 13 error counters in loss.COUNT_FIELDS
+    order, the 14 metrics in Loss.keys order, T).  cfg4: 20 MB in all.  Rank 0 writes
+    <name>.npy, rank r > 0 writes <name>.rank<r>.npy.  The inputs are a function of --seed, so
+    two builds run with the same arguments can be compared file for file."""
+    from loss import counts_to_vector
+    os.makedirs(dirname, exist_ok=True)
+    L = det.L
+    L.resolve()
+    if trials:
+        r, xmmse, var = det.last_shard
+    else:
+        r, xmmse, var = det.last.r, det.last.xmmse, det.last.var
+    pairs = lambda t: torch.view_as_real(t.squeeze(-1).contiguous()).to(torch.float32).cpu().numpy()  # noqa: E731
+    arrays = {'r': pairs(r), 'xmmse': pairs(xmmse), 'var': var.squeeze(-1).to(torch.float32).cpu().numpy(),
+              'counts': counts_to_vector(L.last_counts),
+              'loss': np.array([float(v) for v in L.rates_from_counts(L.last_counts)], dtype=np.float64),
+              'T': np.array([float(L.last_status.T)], dtype=np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    suffix = f'.rank{rank}' if rank else ''
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, f'{name}{suffix}.npy'), a)
+
+
+def unload_if_profiled(nat):
+    """Under rocprofv3 (it names its tool library in ROCP_TOOL_LIBRARIES) the library is closed
+    before the interpreter goes down: its exit-time destructors otherwise run after the profiler
+    has finalised and crash it (amp_native.unload).  Any other run keeps the library loaded to
+    the end of the process, like every test process does, so the code the benchmark ran stays
+    visible in the process's memory map for as long as it lives."""
+    if os.environ.get('ROCP_TOOL_LIBRARIES'):
+        nat.unload()
+
+
 def spawn_ranks(n: int) -> int:
     """`bench.py --gpus N` started without a launcher: start N fresh child processes, one per
     GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as torch.distributed.run sets them), wait for
@@ -180,6 +225,77 @@ def spawn_ranks(n: int) -> int:
     rcs = [p.wait() for p in procs]
     bad = [rc for rc in rcs if rc != 0]
     return (bad[0] if bad[0] > 0 else 1) if bad else 0
+
+
+def kernel_roofline(args, inp, det, step, device, trials, persistent, gname, Bp, T):
+    """--full: the dominant kernel timed in runs of its own, after the timed steps.  Returns
+    (detail.kernel_ms, the roofline block)."""
+    import ctypes as C
+    import amp_native as nat
+    from config import Config
+    from vamp import VAMP
+    Nt, Na, Nr, B, alph, iters = CONFIGS[args.config]
+    # dominant kernel timed with HIP events on the stream it runs on: the persistent engine's
+    # single vamp_persist launch (T iterations: 2 complex mat-vecs per trial-iteration), or the
+    # launch engine's GEMM2 + fused denoiser kernel (one complex mat-vec per trial); trial
+    # sharding profiles the launch engine on this rank's slice (what it runs per iteration)
+    if trials:
+        b0, b1 = det.shard()
+        pcfg = Config(Nt, Na, Nr, 1, 1, batch=Bp, generator_mode='sparc', iterations=iters, alphabet=alph,
+                      channel_profile='uniform', channel_truncation='tail', device='cuda')
+        prof = VAMP(pcfg, engine=nat.ENGINE_LAUNCHES)
+        Tr = prof.detect(inp['U'], inp['s'], inp['Vh'], inp['y'][b0:b1].contiguous(), inp['SNR'])
+    else:
+        Tr = det.detect(inp['U'], inp['s'], inp['Vh'], inp['y'], inp['SNR'])
+    ms = (C.c_float * 4)()
+    nat.check(nat.lib().amp_vamp_profile(C.byref(Tr.dims), C.byref(Tr.const), C.byref(Tr.args), ms, Tr.stream),
+              'amp_vamp_profile')
+    N, k = Nt, min(Nt, Nr)
+    flops_mv = 8.0 * Bp * N * k                    # complex [N x k] . [k] per trial = 8 real flop / CMAC
+    # the fp16x2 engine forms y~ = (s Uh) y in its prologue when n == 2N (amp_vamp.hip): those
+    # 8 B n k flops per trial belong to the launch then
+    ytil_in = persistent and gname == 'fp16x2' and Nr == 2 * Nt and os.environ.get('AMP_YTIL_IN_KERNEL') != '0'
+    if persistent:
+        kern, flops_launch = 'vamp_persist (whole iteration loop: 2 GEMMs + LMMSE + Onsager + denoiser per iteration' + \
+            (', y~ GEMM in the prologue)' if ytil_in else ')'), 2.0 * flops_mv * T + (8.0 * Bp * Nr * k if ytil_in else 0.0)
+        kms = {'prepare': ms[0], 'vamp_persist': ms[1], 'forward': ms[3]}
+    else:
+        kern, flops_launch = 'vamp_k2 (GEMM2 + Onsager update + section denoiser)', flops_mv
+        kms = {'gemm1': ms[0], 'gemm2_denoise': ms[1], 'reduce': ms[2], 'forward': ms[3]}
+    achieved_alone = flops_launch / (ms[1] * 1e-3) / 1e12
+    # the same kernel timed inside a loop of forwards, as the timed region runs it (the standalone
+    # launch above runs ~2-3 % faster: no neighbouring launches, DESIGN.md §3.1): HIP event pairs
+    # the library records around every vamp_persist launch (amp_debug_persist_timing)
+    ms_loop = None
+    if persistent and not trials:
+        nat.check(nat.lib().amp_debug_persist_timing(1), 'amp_debug_persist_timing')
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize(device)
+        nat.check(nat.lib().amp_debug_persist_timing(0), 'amp_debug_persist_timing')
+        n_t, m_t = C.c_int32(0), C.c_float(0.0)
+        nat.check(nat.lib().amp_debug_persist_time(C.byref(n_t), C.byref(m_t)), 'amp_debug_persist_time')
+        if n_t.value == args.steps:
+            ms_loop = float(m_t.value)
+            kms['vamp_persist_in_loop'] = ms_loop
+    achieved = flops_launch / ((ms_loop if ms_loop else ms[1]) * 1e-3) / 1e12
+    traffic, traffic_src = traffic_from_profile(persistent, gname)
+    roofline = {'bound': 'mfma', 'achieved': achieved, 'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                'frac': achieved / FP32_MFMA_PEAK_TFLOPS,
+                'timing': 'in-loop (HIP events around every vamp_persist launch of a loop of forwards)'
+                          if ms_loop else 'standalone launch (HIP events)',
+                'frac_standalone': achieved_alone / FP32_MFMA_PEAK_TFLOPS, 'traffic': traffic,
+                'traffic_source': traffic_src,
+                'kernel': kern, 'flop_per_launch': flops_launch,
+                'gemm': gname}
+    if gname != 'f32':
+        # the f32 products run as six bf16 (bf16x3) or three fp16 (fp16x2) MFMA products each
+        # (amp_persist.h gemm_x3 / gemm_h2): the matrix cores' own rate against the dense peak of
+        # that input type (bf16 and fp16 have the same dense peak on gfx950)
+        mult = 6 if gname == 'bf16x3' else 3
+        roofline[gname[:4] + '_issued'] = {'achieved': mult * achieved, 'peak': BF16_MFMA_PEAK_TFLOPS,
+                                           'frac': mult * achieved / BF16_MFMA_PEAK_TFLOPS}
+    return kms, roofline
 
 
 def main():
@@ -204,6 +320,11 @@ def main():
     ap.add_argument('--shard', default='epochs', choices=['epochs', 'trials'])
     ap.add_argument('--prewarm-ms', type=float, default=300.0,
                     help='untimed steps for this long before the --warmup steps (clock ramp)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (r, xmmse, var, counters, metrics, T) as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also time the dominant kernel alone and in a loop (detail.kernel_ms, roofline) and the '
+                         'CPU baseline: runs of their own, after the timed steps')
     args = ap.parse_args()
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -269,27 +390,17 @@ def main():
     rates = dict(zip(L.keys, L.rates_from_vector(merged, epochs=n_epochs)))
     ver, ser = float(rates['ver']), float(rates['ser'])
 
-    # dominant kernel timed with HIP events on the stream it runs on: the persistent engine's
-    # single vamp_persist launch (T iterations: 2 complex mat-vecs per trial-iteration), or the
-    # launch engine's GEMM2 + fused denoiser kernel (one complex mat-vec per trial); trial
-    # sharding profiles the launch engine on this rank's slice (what it runs per iteration)
+    # the engine and GEMM arithmetic the timed forwards ran (the library's own selection for
+    # their dimensions); trial sharding runs the launch engine on this rank's slice
     if trials:
         b0, b1 = det.shard()
         Bp = b1 - b0
-        pcfg = Config(Nt, Na, Nr, 1, 1, batch=Bp, generator_mode='sparc', iterations=iters, alphabet=alph,
-                      channel_profile='uniform', channel_truncation='tail', device='cuda')
-        prof = VAMP(pcfg, engine=nat.ENGINE_LAUNCHES)
-        Tr = prof.detect(inp['U'], inp['s'], inp['Vh'], inp['y'][b0:b1].contiguous(), inp['SNR'])
+        sel = (cfg.dims(batch=Bp), int(inp['U'].shape[1]), nat.ENGINE_LAUNCHES, nat.GEMM_AUTO)
     else:
         Bp = B
-        Tr = det.detect(inp['U'], inp['s'], inp['Vh'], inp['y'], inp['SNR'])
-    persistent = nat.lib().amp_vamp_select_engine(C.byref(Tr.dims), Tr.k, Tr.args.engine) == nat.ENGINE_PERSISTENT
-    ms = (C.c_float * 4)()
-    nat.check(nat.lib().amp_vamp_profile(C.byref(Tr.dims), C.byref(Tr.const), C.byref(Tr.args), ms, Tr.stream),
-              'amp_vamp_profile')
-    N, k = Nt, min(Nt, Nr)
-    flops_mv = 8.0 * Bp * N * k                    # complex [N x k] . [k] per trial = 8 real flop / CMAC
-    gmode = nat.lib().amp_vamp_select_gemm(C.byref(Tr.dims), Tr.k, Tr.args.gemm) if persistent else nat.GEMM_F32
+        sel = (det.last.dims, det.last.k, det.last.args.engine, det.last.args.gemm)
+    persistent = nat.lib().amp_vamp_select_engine(C.byref(sel[0]), sel[1], sel[2]) == nat.ENGINE_PERSISTENT
+    gmode = nat.lib().amp_vamp_select_gemm(C.byref(sel[0]), sel[1], sel[3]) if persistent else nat.GEMM_F32
     gname = {nat.GEMM_X3: 'bf16x3', nat.GEMM_H2: 'fp16x2', nat.GEMM_I8: 'int8x4'}.get(gmode, 'f32')
     arith = {'bf16x3': 'GEMMs: every f32 operand split into three bf16 pieces (24 significant bits), six '
                        'products per f32 product (dropped terms < 2^-24 relative), f32 accumulation on '
@@ -302,38 +413,15 @@ def main():
                        '(>= 24 significant bits down to 2^-7 of the row/column max; dropped terms < 2^-30 of '
                        'row max . column max); denoiser f32, scalars f32/f64 as the reference',
              'f32': 'GEMMs on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32)'}[gname]
-    # the fp16x2 engine forms y~ = (s Uh) y in its prologue when n == 2N (amp_vamp.hip): those
-    # 8 B n k flops per trial belong to the launch then
-    ytil_in = persistent and gname == 'fp16x2' and Nr == 2 * Nt and os.environ.get('AMP_YTIL_IN_KERNEL') != '0'
-    if persistent:
-        kern, flops_launch = 'vamp_persist (whole iteration loop: 2 GEMMs + LMMSE + Onsager + denoiser per iteration' + \
-            (', y~ GEMM in the prologue)' if ytil_in else ')'), 2.0 * flops_mv * T + (8.0 * Bp * Nr * k if ytil_in else 0.0)
-        kms = {'prepare': ms[0], 'vamp_persist': ms[1], 'forward': ms[3]}
-    else:
-        kern, flops_launch = 'vamp_k2 (GEMM2 + Onsager update + section denoiser)', flops_mv
-        kms = {'gemm1': ms[0], 'gemm2_denoise': ms[1], 'reduce': ms[2], 'forward': ms[3]}
-    achieved_alone = flops_launch / (ms[1] * 1e-3) / 1e12
-    # the same kernel timed inside a loop of forwards, as the timed region runs it (the standalone
-    # launch above runs ~2-3 % faster: no neighbouring launches): HIP event pairs
-    # the library records around every vamp_persist launch (amp_debug_persist_timing)
-    ms_loop = None
-    if persistent and not trials:
-        nat.check(nat.lib().amp_debug_persist_timing(1), 'amp_debug_persist_timing')
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize(device)
-        nat.check(nat.lib().amp_debug_persist_timing(0), 'amp_debug_persist_timing')
-        n_t, m_t = C.c_int32(0), C.c_float(0.0)
-        nat.check(nat.lib().amp_debug_persist_time(C.byref(n_t), C.byref(m_t)), 'amp_debug_persist_time')
-        if n_t.value == args.steps:
-            ms_loop = float(m_t.value)
-            kms['vamp_persist_in_loop'] = ms_loop
-    achieved = flops_launch / ((ms_loop if ms_loop else ms[1]) * 1e-3) / 1e12
-    traffic, traffic_src = traffic_from_profile(persistent, gname)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, det, trials, rank)   # before --full's own forwards reuse the buffers
+    kms = roofline = None
+    if args.full:
+        kms, roofline = kernel_roofline(args, inp, det, step, device, trials, persistent, gname, Bp, T)
     if rank != 0:
         if dist:
             tdist.destroy_process_group()
-        nat.unload()
+        unload_if_profiled(nat)
         return
     ms_step = el / args.steps * 1e3
     gb = B if trials else world * B                # trials detected per step, all ranks together
@@ -354,33 +442,21 @@ def main():
                    'global_batch': gb, 'shard': args.shard, 'parallelism': par},
         'detail': {'T': T, 'ver': ver, 'ser': ser, 'epochs': n_epochs,
                    'trial_iterations_per_s': gb * T / (el / args.steps),
-                   'engine': 'persistent' if persistent else 'launches', 'kernel_ms': kms,
+                   'engine': 'persistent' if persistent else 'launches',
                    'arithmetic': arith,
                    'grid_rescues': int(getattr(det, 'grid_rescues', 0)),
                    'prewarm': {'ms': args.prewarm_ms, 'steps': npre,
                                'why': 'untimed steps before --warmup: the clocks ramp over the first ~25 ms'}},
-        'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                     'frac': achieved / FP32_MFMA_PEAK_TFLOPS,
-                     'timing': 'in-loop (HIP events around every vamp_persist launch of a loop of forwards)'
-                               if ms_loop else 'standalone launch (HIP events)',
-                     'frac_standalone': achieved_alone / FP32_MFMA_PEAK_TFLOPS, 'traffic': traffic,
-                     'traffic_source': traffic_src,
-                     'kernel': kern, 'flop_per_launch': flops_launch,
-                     'gemm': gname},
     }
-    if gname != 'f32':
-        # the f32 products run as six bf16 (bf16x3) or three fp16 (fp16x2) MFMA products each
-        # (amp_persist.h gemm_x3 / gemm_h2): the matrix cores' own rate against the dense peak of
-        # that input type (bf16 and fp16 have the same dense peak on gfx950)
-        mult = 6 if gname == 'bf16x3' else 3
-        out['roofline'][gname[:4] + '_issued'] = {'achieved': mult * achieved, 'peak': BF16_MFMA_PEAK_TFLOPS,
-                                                 'frac': mult * achieved / BF16_MFMA_PEAK_TFLOPS}
-    if not args.no_cpu_baseline and world == 1:
-        out['cpu_baseline'] = cpu_baseline(args.config, args.ebn0, args.seed, args.cpu_sample)
+    if args.full:
+        out['detail']['kernel_ms'] = kms
+        out['roofline'] = roofline
+        if not args.no_cpu_baseline and world == 1:
+            out['cpu_baseline'] = cpu_baseline(args.config, args.ebn0, args.seed, args.cpu_sample)
     print(json.dumps(out), flush=True)
     if dist:
         tdist.destroy_process_group()
-    nat.unload()
+    unload_if_profiled(nat)
 
 
 if __name__ == '__main__':

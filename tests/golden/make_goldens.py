@@ -59,6 +59,9 @@ import bamp as ref_bamp      # noqa: E402
 import scamp as ref_scamp    # noqa: E402
 import shrink as ref_shrink  # noqa: E402
 
+sys.path.append(os.path.dirname(HERE))      # tests/, after everything else: the fixture readers
+from golden_io import save_parts            # noqa: E402
+
 torch.set_num_threads(int(os.environ.get('GOLDEN_THREADS', '8')))
 
 
@@ -197,7 +200,7 @@ def g1():
     for key, rec in out.items():
         for k, v in rec.items():
             flat[f'{key}/{k}'] = np.asarray(v)
-    np.savez_compressed(os.path.join(HERE, 'g1_traces.npz'), **flat)
+    save_parts('g1_traces', flat)       # larger than 1 MiB in one file: g1_traces.part<k>.npz
 
 
 # ---------------------------------------------------------------------------
@@ -367,7 +370,7 @@ def g5():
                          f'{key}/sw_x': c(xs), f'{key}/sw_var': c(vs), f'{key}/overflow': np.array(1)})
             n += 1
     flat['ncases'] = np.array(n)
-    np.savez_compressed(os.path.join(HERE, 'g5_shrink.npz'), **flat)
+    save_parts('g5_shrink', flat)       # larger than 1 MiB in one file: g5_shrink.part<k>.npz
     print('g5 cases', n)
 
 

@@ -22,9 +22,66 @@ def _group(npz):
     return out
 
 
+PART_LIMIT = 1000000     # no committed file is larger than 1 MiB; this leaves a margin
+
+
+class Parts:
+    """The arrays of tests/golden/<stem>.part<k>.npz, k = 0, 1, ..., read like one npz file: a
+    fixture that would be larger than PART_LIMIT in one file is stored in parts (save_parts)."""
+
+    def __init__(self, stem):
+        self._of = {}
+        k = 0
+        while os.path.exists(os.path.join(GOLDEN, f'{stem}.part{k}.npz')):
+            z = np.load(os.path.join(GOLDEN, f'{stem}.part{k}.npz'))
+            for name in z.files:
+                assert name not in self._of, (stem, name)
+                self._of[name] = z
+            k += 1
+        if not k:
+            raise FileNotFoundError(os.path.join(GOLDEN, f'{stem}.part0.npz'))
+        self.files = list(self._of)
+
+    def __getitem__(self, name):
+        return self._of[name][name]
+
+
+def save_parts(stem, flat, limit=PART_LIMIT):
+    """Writes the arrays `flat` ('<case>/<field>': array) as tests/golden/<stem>.part<k>.npz, each
+    at most `limit` bytes: whole cases in their given order, a new part begun when the next case
+    would take the current one over the limit.  Removes the parts of an earlier, longer run."""
+    import io
+    cases = {}
+    for name, a in flat.items():
+        cases.setdefault(name.split('/', 1)[0], {})[name] = a
+
+    def packed(arrays):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **arrays)
+        return buf.getvalue()
+
+    parts, cur = [], {}
+    for arrays in cases.values():
+        if cur and len(packed({**cur, **arrays})) > limit:
+            parts.append(cur)
+            cur = {}
+        cur.update(arrays)
+    parts.append(cur)
+    for k, arrays in enumerate(parts):
+        raw = packed(arrays)
+        assert len(raw) <= limit, (stem, k, len(raw))
+        with open(os.path.join(GOLDEN, f'{stem}.part{k}.npz'), 'wb') as f:
+            f.write(raw)
+    k = len(parts)
+    while os.path.exists(os.path.join(GOLDEN, f'{stem}.part{k}.npz')):
+        os.remove(os.path.join(GOLDEN, f'{stem}.part{k}.npz'))
+        k += 1
+    return len(parts)
+
+
 def g1_cases():
     """{name: Case} — per-iteration reference traces with their stored inputs."""
-    cases = _group(np.load(os.path.join(GOLDEN, 'g1_traces.npz')))
+    cases = _group(Parts('g1_traces'))
     for name, c in cases.items():
         algo, alph, ebn0, seed = name.split('_')
         c['algo'], c['alphabet'], c['EbN0'], c['seed'] = algo, alph, float(ebn0), int(seed)

@@ -1,4 +1,4 @@
-"""g5 Shrink golden cases (tests/golden/g5_shrink.npz) with the inputs the kernels need."""
+"""g5 Shrink golden cases (tests/golden/g5_shrink.part*.npz) with the inputs the kernels need."""
 import numpy as np
 import torch
 
@@ -7,7 +7,7 @@ from config import Config
 
 
 def g5_cases():
-    z = gio._group(np.load(gio.GOLDEN + '/g5_shrink.npz'))
+    z = gio._group(gio.Parts('g5_shrink'))
     out = []
     for name, c in sorted(z.items(), key=lambda kv: int(kv[0][4:])):
         Nt, Na, B = (int(v) for v in c.dims)

@@ -17,7 +17,7 @@ step() {
 }
 export AMP_PERSIST_LAUNCH=coop
 step tests 600 python -u -m pytest tests/test_gpu_vamp.py tests/test_gpu_bamp_scamp.py -m gpu -q -x --timeout 120 --timeout-method thread
-step bench 300 python bench.py --no-cpu-baseline
+step bench 300 python bench.py --full --no-cpu-baseline
 step prof_unload 150 rocprofv3 --kernel-trace --stats -d $O/pu -o p --output-format csv -- python3 tools/exit_probe.py persistent profile unload
 step prof_plain 150 rocprofv3 --kernel-trace --stats -d $O/pp -o p --output-format csv -- python3 tools/exit_probe.py persistent profile keep
 echo "=== done"

@@ -26,20 +26,20 @@ run_nogate() {   # a step whose failures are data (e.g. the list of failing T ch
 PYT="python3 -u -m pytest -x -q --timeout 120 --timeout-method thread"
 for s in ${STEPS:-bench}; do
     case $s in
-    bench) run bench 300 python3 bench.py ;;
-    bench_nocpu) run bench_nocpu 300 python3 bench.py --no-cpu-baseline ;;
-    bench_h2) run bench_h2 300 python3 bench.py --no-cpu-baseline --gemm h2 ;;
-    bench_w8) run bench_w8 300 env AMP_VAMP_X3_WAVES=8 python3 bench.py --no-cpu-baseline ;;
+    bench) run bench 300 python3 bench.py --full ;;
+    bench_nocpu) run bench_nocpu 300 python3 bench.py --full --no-cpu-baseline ;;
+    bench_h2) run bench_h2 300 python3 bench.py --full --no-cpu-baseline --gemm h2 ;;
+    bench_w8) run bench_w8 300 env AMP_VAMP_X3_WAVES=8 python3 bench.py --full --no-cpu-baseline ;;
     trace_w8) run trace_w8 300 env AMP_VAMP_X3_WAVES=8 python3 tools/trace_persist.py --config cfg4 ;;
     tests_w8) run tests_w8 900 env AMP_VAMP_X3_WAVES=8 $PYT tests/test_gpu_vamp.py -m gpu -k "persistent and not f32 and not h2 and not i8" ;;
-    ab_w8) run ab_def 300 python3 bench.py --no-cpu-baseline &&
-           run ab_pin 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_w8pin.so python3 bench.py --no-cpu-baseline &&
-           run ab_du1 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_w8du1.so python3 bench.py --no-cpu-baseline &&
-           run ab_def2 300 python3 bench.py --no-cpu-baseline ;;
-    bench_i8) run bench_i8 300 python3 bench.py --no-cpu-baseline --gemm i8 ;;
+    ab_w8) run ab_def 300 python3 bench.py --full --no-cpu-baseline &&
+           run ab_pin 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_w8pin.so python3 bench.py --full --no-cpu-baseline &&
+           run ab_du1 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_w8du1.so python3 bench.py --full --no-cpu-baseline &&
+           run ab_def2 300 python3 bench.py --full --no-cpu-baseline ;;
+    bench_i8) run bench_i8 300 python3 bench.py --full --no-cpu-baseline --gemm i8 ;;
     trace_i8) run trace_i8 300 python3 tools/trace_persist.py --config cfg4 --gemm i8 ;;
     tests_i8) run tests_i8 900 $PYT tests/test_gpu_vamp.py -m gpu -k "i8 or split_engines" ;;
-    bench_f32) run bench_f32 300 python3 bench.py --no-cpu-baseline --gemm f32 ;;
+    bench_f32) run bench_f32 300 python3 bench.py --full --no-cpu-baseline --gemm f32 ;;
     trace) run trace 300 python3 tools/trace_persist.py --config cfg4 ;;
     trace_h2) run trace_h2 300 env AMP_VAMP_GEMM=h2 python3 tools/trace_persist.py --config cfg4 ;;
     configs) run configs 600 python3 tools/configs_bench.py ;;
@@ -100,27 +100,27 @@ for s in ${STEPS:-bench}; do
     tprobe_diag) for v in ${DIAGS:-expdiv}; do
                 run tprobe_$v 600 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_$v.so python3 tools/t_probe.py || exit 1
             done ;;
-    ab_pkg0) run ab_def 300 python3 bench.py --no-cpu-baseline &&
-             run ab_pkg0 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_pkg0.so python3 bench.py --no-cpu-baseline &&
-             run ab_def2 300 python3 bench.py --no-cpu-baseline &&
-             run ab_pkg0_2 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_pkg0.so python3 bench.py --no-cpu-baseline &&
+    ab_pkg0) run ab_def 300 python3 bench.py --full --no-cpu-baseline &&
+             run ab_pkg0 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_pkg0.so python3 bench.py --full --no-cpu-baseline &&
+             run ab_def2 300 python3 bench.py --full --no-cpu-baseline &&
+             run ab_pkg0_2 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_pkg0.so python3 bench.py --full --no-cpu-baseline &&
              run ab_cfg3 300 python3 tools/configs_bench.py cfg3 cfg3-qpsk &&
              run ab_cfg3_pkg0 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_pkg0.so python3 tools/configs_bench.py cfg3 cfg3-qpsk ;;
-    ab_stg) run ab_stg_def 300 python3 bench.py --no-cpu-baseline &&
-            run ab_stg0 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_stg0.so python3 bench.py --no-cpu-baseline &&
-            run ab_stg_def2 300 python3 bench.py --no-cpu-baseline &&
-            run ab_stg0_2 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_stg0.so python3 bench.py --no-cpu-baseline ;;
+    ab_stg) run ab_stg_def 300 python3 bench.py --full --no-cpu-baseline &&
+            run ab_stg0 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_stg0.so python3 bench.py --full --no-cpu-baseline &&
+            run ab_stg_def2 300 python3 bench.py --full --no-cpu-baseline &&
+            run ab_stg0_2 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_stg0.so python3 bench.py --full --no-cpu-baseline ;;
     # A/B of a diagnostic library (lib_diag/libampsparc_$DIAG.so) against the default on one box
     ab) D=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_${DIAG:-tgr}.so
-        run ab_def 300 python3 bench.py --no-cpu-baseline &&
-        run ab_${DIAG:-tgr} 300 env AMP_LIB_PATH=$D python3 bench.py --no-cpu-baseline &&
-        run ab_def2 300 python3 bench.py --no-cpu-baseline &&
-        run ab_${DIAG:-tgr}_2 300 env AMP_LIB_PATH=$D python3 bench.py --no-cpu-baseline ;;
+        run ab_def 300 python3 bench.py --full --no-cpu-baseline &&
+        run ab_${DIAG:-tgr} 300 env AMP_LIB_PATH=$D python3 bench.py --full --no-cpu-baseline &&
+        run ab_def2 300 python3 bench.py --full --no-cpu-baseline &&
+        run ab_${DIAG:-tgr}_2 300 env AMP_LIB_PATH=$D python3 bench.py --full --no-cpu-baseline ;;
     # A/B of an environment switch (ENVAB="NAME=value") against the default on one box
-    ab_env) run abe_def 300 python3 bench.py --no-cpu-baseline &&
-            run abe_env 300 env $ENVAB python3 bench.py --no-cpu-baseline &&
-            run abe_def2 300 python3 bench.py --no-cpu-baseline &&
-            run abe_env2 300 env $ENVAB python3 bench.py --no-cpu-baseline ;;
+    ab_env) run abe_def 300 python3 bench.py --full --no-cpu-baseline &&
+            run abe_env 300 env $ENVAB python3 bench.py --full --no-cpu-baseline &&
+            run abe_def2 300 python3 bench.py --full --no-cpu-baseline &&
+            run abe_env2 300 env $ENVAB python3 bench.py --full --no-cpu-baseline ;;
     tests_ytil) run tests_ytil 300 $PYT tests/test_gpu_vamp.py -m gpu -k "ytil or engines_agree or n256 or x3_gemm" ;;
     trace_diag) run trace_${DIAG:-tgr} 300 env AMP_LIB_PATH=amp-sparc-spatialmodulation_amd/lib_diag/libampsparc_${DIAG:-tgr}.so python3 tools/trace_persist.py --config cfg4 ;;
     configs_res1) run configs_res1 300 python3 tools/configs_bench.py cfg2 cfg2-epochs8 cfg2-res1 ;;

@@ -23,7 +23,7 @@ def main(src, dst):
     out = []
     stats = os.path.join(src, 'kt', 'kt_kernel_stats.csv')
     rows = list(csv.DictReader(open(stats)))
-    out.append('# rocprofv3 --kernel-trace --stats  (bench.py --no-cpu-baseline; cfg4 VAMP)')
+    out.append('# rocprofv3 --kernel-trace --stats  (bench.py --full --no-cpu-baseline; cfg4 VAMP)')
     out.append(f'{"kernel":44s} {"calls":>6s} {"avg_us":>9s} {"total_us":>10s} {"pct":>6s}')
     for r in sorted(rows, key=lambda r: -float(r['TotalDurationNs'])):
         out.append(f'{short(r["Name"])[:44]:44s} {int(r["Calls"]):6d} {float(r["AverageNs"]) / 1e3:9.2f} '
@@ -33,7 +33,7 @@ def main(src, dst):
         for r in csv.DictReader(open(f)):
             pmc[short(r['Kernel_Name'])][r['Counter_Name']].append(float(r['Counter_Value']))
     out.append('')
-    out.append('# PMC, average per dispatch (separate --pmc passes, bench.py --steps 1 --warmup 0)')
+    out.append('# PMC, average per dispatch (separate --pmc passes, bench.py --full --steps 1 --warmup 0)')
     for k in sorted(pmc):
         if not k.startswith('amp::'):
             continue
