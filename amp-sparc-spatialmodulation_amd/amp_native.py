@@ -65,6 +65,14 @@ class AmpVampDecideArgs(C.Structure):
                 ('pad', C.c_int32), ('counts', C.c_void_p), ('host_record', C.c_void_p)]
 
 
+class AmpTrialsDecideArgs(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('sym', C.c_void_p), ('idx', C.c_void_p), ('ibits_trunc', C.c_int32),
+                ('rule', C.c_int32), ('counts', C.c_void_p)]
+
+
+RULE_SPARC, RULE_SEGMENTED = 0, 1
+
+
 class AmpVampShard(C.Structure):
     _fields_ = [('xbuf', C.c_void_p), ('xbuf_bytes', C.c_size_t), ('B_global', C.c_int32), ('row_offset', C.c_int32),
                 ('gen', C.c_uint32), ('pad', C.c_int32)]
@@ -131,6 +139,10 @@ SIGNATURES = {
     'amp_vamp_shard_reset': (C.c_int, [_P, _P]),
     'amp_vamp_detect_count_shard': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), C.POINTER(AmpVampDecideArgs),
                                               C.POINTER(AmpVampShard), _P]),
+    'amp_vamp_trials_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I]),
+    'amp_vamp_trials_run': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _P]),
+    'amp_bamp_trials_workspace_bytes': (C.c_size_t, [_D, _I, _I]),
+    'amp_bamp_trials_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _P]),
     'amp_bamp_workspace_bytes': (C.c_size_t, [_D, _I]),
     'amp_bamp_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),
     'amp_bamp_prepare': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),

@@ -192,6 +192,48 @@ class BAMP(LazyResult, nn.Module):
         self.last = T
         return self.L
 
+    def forward_trials(self, H: torch.Tensor, ys, SNR: float, xs, symbols, indices) -> list:
+        """E independent single-trial detections that share ONE channel H and one SNR, in one
+        launch sequence (amp_bamp_trials_run) — the epochs of one `res` block of the reference's
+        drivers, which run batch = 1 (bamp_model.py:89, 96).  Each trial is the B = 1 forward of
+        that trial alone: its own max|xi| shift (bamp.py:70), its own allclose exit and iteration
+        count (bamp.py:140), decided and counted as Loss at B = 1 in generator_mode 'sparc' or
+        'segmented'.  Returns E Loss objects (in order) that equal E sequential forward() calls;
+        they resolve lazily.  ys / xs / symbols / indices as VAMP.forward_trials.
+        ValueError unless config.B == 1."""
+        E = self._trials_check(ys, xs, symbols, indices)
+        dev = ys[0].device
+        with torch.cuda.device(dev):
+            cfg = self.config
+            n, N = H.shape[-2], H.shape[-1]
+            Hc = _c64(H, (n, N))
+            y, x, sym, idx, res, host, dec = self._trials_inputs(ys, xs, symbols, indices, E, n, dev)
+            d, cst = cfg.dims(), cfg.constellation()
+            lib = nat.lib()
+            wsb = lib.amp_bamp_trials_workspace_bytes(C.byref(d), cfg.N_Layers, E)
+            if wsb == 0:
+                raise ValueError('amp_bamp_trials_workspace_bytes: invalid dimensions')
+            ws = nat.WORKSPACE.get(dev, 'bamp_trials', wsb)
+            xmap = torch.empty(E, N, dtype=torch.complex64, device=dev)
+            xm = torch.empty_like(xmap)
+            var = torch.empty(E, N, dtype=torch.float32, device=dev)
+            a = nat.AmpBampArgs()
+            a.H, a.y = nat.dptr(Hc, name='H'), nat.dptr(y, name='y')
+            a.max_iter = cfg.N_Layers
+            a.denoiser = 0
+            a.noise_var = float(self.E / SNR)                                  # bamp.py:124
+            a.P0, a.Ps = float(np.float32(cfg.P0)), float(np.float32(cfg.Ps))
+            a.gemm = self.gemm
+            a.xmap, a.xmmse, a.var = nat.dptr(xmap), nat.dptr(xm), nat.dptr(var)
+            a.status = nat.dptr(res)
+            a.ws, a.ws_bytes = nat.dptr(ws), ws.numel()
+            nat.check(lib.amp_bamp_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
+                                              nat.stream_ptr(dev)), 'amp_bamp_trials_run')
+            out = self._trials_losses(res, host, E, dev)
+            self._trials_keep = (y, x, sym, idx, Hc)   # alive until the kernels have read them
+            self.last_trials = (xmap.view(E, 1, N, 1), xm.view(E, 1, N, 1), var.view(E, 1, N, 1))
+        return out
+
 
 class ShardedBAMP(ShardHook, BAMP):
     """SURVEY §8(e) exact-compat mode for BAMP: ONE batch split over the ranks of

@@ -88,7 +88,7 @@ def svd_gram(A: torch.Tensor, max_cond: float = 20.0):
 class Model(nn.Module):
     def __init__(self, config: Config, detector: str = 'vamp', path: str | None = None, amp=None,
                  seed: int | None = None, rng: str = 'host', group_epochs: bool = False,
-                 shard: str = 'epochs') -> None:
+                 shard: str = 'epochs', group_trials: int = 0) -> None:
         """rng='host' (default): the reference's numpy / torch-CPU random streams, bit for bit
         (parity mode).  rng='device': channel, messages and noise drawn on the GPU and the SVD
         on the GPU through the Gram matrix's eigendecomposition (svd_gram; throughput mode: same
@@ -96,6 +96,11 @@ class Model(nn.Module):
         group_epochs: VAMP detects up to max_epochs of its epochs side by side in one persistent
         launch (VAMP.forward_epochs: one channel per epoch, or one per `res` block; same results,
         fills the GPU at small B).
+        group_trials (> 0, config.B == 1, VAMP / BAMP): the reference's own way to run — batch = 1,
+        `res` epochs per channel (vamp_model.py:91, 98) — with the runs of epochs that share a
+        channel detected as independent trials in one launch sequence (forward_trials), in chunks
+        of at most group_trials; every trial keeps its own scalars, shift and exit, so the sweep
+        equals the per-epoch loop.  res = 1 degenerates to single forward calls.
         shard (with torch.distributed): 'epochs' (default) gives each rank whole epochs with its
         own random stream and merges the metrics once per SNR point; 'trials' (SURVEY §8(e)
         exact-compat, VAMP / BAMP / SCAMP) gives every rank the SAME epochs (one seed) and splits each batch's
@@ -150,6 +155,16 @@ class Model(nn.Module):
                 raise ValueError('group_epochs: side-by-side epochs are built for the VAMP detector')
             N, n = config.Nt * config.Lin, config.Nr * config.Lout
             self.group_cap = self.amp.max_epochs(min(n, N))
+        self.trials_cap = 0
+        if group_trials:
+            if group_trials < 0:
+                raise ValueError(f'group_trials must be >= 0, got {group_trials}')
+            if config.B != 1 or detector not in ('vamp', 'bamp') or not hasattr(self.amp, 'forward_trials'):
+                raise ValueError('group_trials: independent-trial batches are built for the VAMP and BAMP '
+                                 'detectors at config.B == 1')
+            if shard == 'trials' or group_epochs:
+                raise ValueError('group_trials does not combine with group_epochs or trial sharding')
+            self.trials_cap = int(group_trials)
 
     # one epoch, in the reference's random-call order (vamp_model.py:55-61)
     def _epoch(self, SNR: float, new_channel: bool):
@@ -200,6 +215,36 @@ class Model(nn.Module):
                 out += self.amp.forward_epochs(U, s, Vh, [v[3] for v in run], SNR, [v[0] for v in run],
                                                [v[1] for v in run], [v[2] for v in run])
         return out
+
+    def _group_trials(self, SNR: float, ids: list, res: int):
+        """The epochs `ids` (this rank's, in order), each drawn in the reference's call order (the
+        channel first when i % res == 0, then message + noise: vamp_model.py:55-61); the runs of
+        epochs that share a channel go through forward_trials in chunks of at most trials_cap, a
+        run of one through the plain forward.  Yields the epochs' Losses in order (the caller
+        accumulates each before the next detection, as the per-epoch loop does)."""
+        run = []
+
+        def flush():
+            if len(run) == 1:
+                x, sym, idx, y = run[0]
+                if self.detector == 'vamp':
+                    yield self.amp(*self._svd, y, SNR, x, sym, idx)
+                else:
+                    yield self.amp(self._A, y, SNR, x, sym, idx)
+            elif run:
+                cols = [[v[j] for v in run] for j in (3, 0, 1, 2)]        # ys, xs, symbols, indices
+                if self.detector == 'vamp':
+                    yield from self.amp.forward_trials(*self._svd, cols[0], SNR, *cols[1:])
+                else:
+                    yield from self.amp.forward_trials(self._A, cols[0], SNR, *cols[1:])
+            run.clear()
+
+        for i in ids:
+            new = i % res == 0
+            if new or len(run) >= self.trials_cap:
+                yield from flush()         # before the next channel replaces this run's
+            run.append(self._inputs(SNR, new))
+        yield from flush()
 
     def _per_epoch_channels(self) -> bool:
         """Whether one launch may hold epochs with different channels (VAMP.epochs_channels_eligible)."""
@@ -268,6 +313,9 @@ class Model(nn.Module):
             mine = [i for i in range(epochs) if (i // res) % self._epoch_world == self.rank % self._epoch_world]
             if self.group_cap > 1:
                 for loss in self._group(SNR, mine, res):      # side by side, chunks of group_cap epochs
+                    self.loss.accumulate(loss)
+            elif self.trials_cap > 0:
+                for loss in self._group_trials(SNR, mine, res):   # independent trials per channel run
                     self.loss.accumulate(loss)
             else:
                 for i in mine:

@@ -235,6 +235,84 @@ class LazyResult:
                 return status, counts
         raise RuntimeError(f'{what}: persistent engine grid barrier timed out (results invalid)')
 
+    # ---- independent-trial batches (forward_trials of VAMP / BAMP) ----
+    _trials_prev = ()
+    _trials_ring = None
+    _trials_i = 1
+
+    def _trials_check(self, ys, xs, symbols, indices) -> int:
+        cfg = self.config
+        if cfg.B != 1:
+            raise ValueError(f'forward_trials: independent trials are B = 1 detections (config.B = {cfg.B}); '
+                             'a B > 1 batch shares its scalars, its shift and its exit (use forward)')
+        if cfg.mode not in ('sparc', 'segmented'):
+            raise ValueError(f"forward_trials: generator_mode {cfg.mode!r} has no independent-trial form "
+                             "('sparc' and 'segmented' only)")
+        E = len(ys)
+        if not (E == len(xs) == len(symbols) == len(indices)) or E < 1:
+            raise ValueError('forward_trials: ys, xs, symbols and indices must hold the same number (>= 1) of trials')
+        return E
+
+    def _trials_slot(self, device, nbytes):
+        """One of two (device, pinned host) result buffers for forward_trials, alternating per
+        call (as _result_slot): a call's records stay readable while the next call runs."""
+        if self._trials_ring is None or self._trials_ring[0][0].device != device or \
+                self._trials_ring[0][0].numel() < nbytes:
+            self._trials_ring = [(torch.zeros(nbytes, dtype=torch.uint8, device=device),
+                                  torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True)) for _ in range(2)]
+        self._trials_i ^= 1
+        d, h = self._trials_ring[self._trials_i]
+        return d[:nbytes], h[:nbytes]
+
+    def _trials_inputs(self, ys, xs, symbols, indices, E, n, dev):
+        """The trials' rows back to back: y [E, n], x [E, N], labels [E * L]; and the decision
+        arguments (Loss at B = 1 per trial, loss.py:20, 38-43) with a result slot holding
+        amp_status[E] then amp_counts[E]."""
+        from loss import _as_device_labels, _flat_c64
+        cfg = self.config
+        stack = lambda v, f: (f(v, E) if isinstance(v, torch.Tensor) else torch.cat([f(u, 1) for u in v]))  # noqa: E731
+        y = stack(ys, lambda v, e: _c64(v, (e, n))).contiguous()
+        x = stack(xs, lambda v, e: _flat_c64(v, e, 'x')).contiguous()
+        sym = stack(symbols, lambda v, e: _as_device_labels(v, dev).reshape(-1)).contiguous()
+        idx = stack(indices, lambda v, e: _as_device_labels(v, dev).reshape(-1)).contiguous()
+        S = E * cfg.Na * cfg.Lin             # sections (Config.L exists in 'sparc' mode only)
+        if sym.numel() != S or idx.numel() != S:
+            raise ValueError(f'expected {S} labels/indices, got {sym.numel()}/{idx.numel()}')
+        st_sz, ct_sz = C.sizeof(nat.AmpStatus), C.sizeof(nat.AmpCounts)
+        res, host = self._trials_slot(dev, E * (st_sz + ct_sz))
+        dec = nat.AmpTrialsDecideArgs()
+        dec.x, dec.sym, dec.idx = nat.dptr(x, name='x'), nat.dptr(sym, name='symbols'), nat.dptr(idx, name='indices')
+        dec.ibits_trunc = self.L._ibits
+        dec.rule = nat.RULE_SEGMENTED if cfg.mode == 'segmented' else nat.RULE_SPARC
+        dec.counts = nat.dptr(res) + E * st_sz
+        return y, x, sym, idx, res, host, dec
+
+    def _trials_losses(self, res, host, E, dev) -> list:
+        """E Loss objects over the call's records, resolved lazily (one copy, one event; the
+        previous call's Losses are resolved here, after this call's launches are queued)."""
+        st_sz, ct_sz = C.sizeof(nat.AmpStatus), C.sizeof(nat.AmpCounts)
+        host[:res.numel()].copy_(res, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        for L in self._trials_prev:
+            L.resolve()
+        out = []
+
+        def finish(L, e):
+            done.synchronize()
+            raw = host.numpy()
+            status = nat.AmpStatus.from_buffer_copy(raw[e * st_sz:(e + 1) * st_sz].tobytes())
+            counts = nat.AmpCounts.from_buffer_copy(raw[E * st_sz + e * ct_sz:E * st_sz + (e + 1) * ct_sz].tobytes())
+            L.last_counts, L.last_status = counts, status
+            L.record(L.rates_from_counts(counts), int(status.T))
+
+        for e in range(E):
+            L = Loss(self.config)
+            L._pending = (lambda L=L, e=e: finish(L, e))
+            out.append(L)
+        self._trials_prev = out
+        return out
+
 
 
 class VAMP(LazyResult, nn.Module):
@@ -463,6 +541,53 @@ class VAMP(LazyResult, nn.Module):
         self._epochs_prev = out
         self._epochs_keep = (y, x, sym, idx, Uc, Vhc, sc)   # alive until the kernels have read them
         self.last_epochs = (r.view(E, B, N, 1), xm.view(E, B, N, 1), var.view(E, B, N, 1))
+        return out
+
+    def forward_trials(self, U, s, Vh, ys, SNR: float, xs, symbols, indices) -> list:
+        """E independent single-trial detections that share ONE channel (U, s, Vh) and one SNR, in
+        one launch sequence (amp_vamp_trials_run) — the epochs of one `res` block of the
+        reference's drivers, which run batch = 1 (vamp_model.py:91, 98).  Each trial is the B = 1
+        forward of that trial alone: its own var.mean() (vamp.py:85), its own max|xi| shift
+        (vamp.py:112), its own allclose exit and iteration count (vamp.py:185), decided and counted
+        as Loss at B = 1 in generator_mode 'sparc' or 'segmented'.  Returns E Loss objects (in
+        order) that equal E sequential forward() calls; they resolve lazily, like forward_epochs'.
+        ys / xs: sequences of the trials' y [1, n, 1] and x [1, N, 1], or stacked [E, ...] tensors;
+        symbols / indices: sequences of their label arrays or stacked label tensors.
+        ValueError unless config.B == 1."""
+        E = self._trials_check(ys, xs, symbols, indices)
+        if self.engine == nat.ENGINE_PERSISTENT:
+            raise ValueError('forward_trials runs on the launch engine (the persistent engine has no '
+                             'independent-trial form)')
+        dev = ys[0].device
+        with torch.cuda.device(dev):
+            cfg = self.config
+            n, k, N = U.shape[-2], U.shape[-1], Vh.shape[-1]
+            Uc = _c64(U, (n, k))
+            sc = s.reshape(k).to(torch.float32).resolve_neg().contiguous()
+            Vhc = _c64(Vh, (k, N))
+            y, x, sym, idx, res, host, dec = self._trials_inputs(ys, xs, symbols, indices, E, n, dev)
+            d, cst = cfg.dims(), cfg.constellation()
+            lib = nat.lib()
+            wsb = lib.amp_vamp_trials_workspace_bytes(C.byref(d), k, cfg.N_Layers, E)
+            if wsb == 0:
+                raise ValueError('amp_vamp_trials_workspace_bytes: invalid dimensions')
+            ws = nat.WORKSPACE.get(dev, 'vamp_trials', wsb)
+            r = torch.empty(E, N, dtype=torch.complex64, device=dev)
+            xm = torch.empty_like(r)
+            var = torch.empty(E, N, dtype=torch.float32, device=dev)
+            a = nat.AmpVampArgs()
+            a.U, a.s, a.Vh, a.y = nat.dptr(Uc, name='U'), nat.dptr(sc, torch.float32, 's'), \
+                nat.dptr(Vhc, name='Vh'), nat.dptr(y, name='y')
+            a.k, a.max_iter, a.engine, a.gemm = k, cfg.N_Layers, self.engine, self.gemm
+            a.noise_var, a.sparsity = float(self.E / SNR), float(self.sparsity)
+            a.r, a.xmmse, a.var = nat.dptr(r), nat.dptr(xm), nat.dptr(var)
+            a.status = nat.dptr(res)
+            a.ws, a.ws_bytes = nat.dptr(ws), ws.numel()
+            nat.check(lib.amp_vamp_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
+                                              nat.stream_ptr(dev)), 'amp_vamp_trials_run')
+            out = self._trials_losses(res, host, E, dev)
+            self._trials_keep = (y, x, sym, idx, Uc, sc, Vhc)   # alive until the kernels have read them
+            self.last_trials = (r.view(E, 1, N, 1), xm.view(E, 1, N, 1), var.view(E, 1, N, 1))
         return out
 
     _epochs_prev = ()
