@@ -116,6 +116,11 @@ SIGNATURES = {
     'amp_vamp_finalize': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), _P]),
     'amp_vamp_profile': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), C.POINTER(C.c_float), _P]),
     'amp_vamp_detect_count': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), C.POINTER(AmpVampDecideArgs), _P]),
+    # operator reuse across forwards on one channel: the same calls with a trailing `reuse` flag
+    'amp_vamp_run_reuse': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), _I, _P]),
+    'amp_vamp_detect_count_reuse': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), C.POINTER(AmpVampDecideArgs), _I, _P]),
+    'amp_vamp_persist_trace_reuse': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), _P, _I, _P]),
+    'amp_vamp_debug_prepare_counts': (C.c_int, [C.POINTER(C.c_uint64)]),
     'amp_vamp_epochs_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I]),
     'amp_vamp_debug_offsets': (C.c_int, [_D, _I, _I, _I, C.POINTER(C.c_uint64)]),
     'amp_vamp_debug_dump': (C.c_int, [_P]),
@@ -283,6 +288,14 @@ def fold_launch() -> bool:
     the host record (amp_host.h fold_in_kernel)."""
     return bool(os.environ.get('AMP_LIB_PATH')) and (os.environ.get('AMP_FOLD_LAUNCH') == '1' or
                                                     os.environ.get('AMP_HOST_RECORD') == '0')
+
+
+def prepare_counts() -> tuple:
+    """(building, reuse) persistent-engine prepares of this process so far
+    (amp_vamp_debug_prepare_counts): whether a forward packed the operators or reused them."""
+    out = (C.c_uint64 * 2)()
+    check(lib().amp_vamp_debug_prepare_counts(out), 'amp_vamp_debug_prepare_counts')
+    return int(out[0]), int(out[1])
 
 
 # amp_status.gemm (include/amp_sparc.h AMP_ARITH_*): the GEMM arithmetic a forward ran

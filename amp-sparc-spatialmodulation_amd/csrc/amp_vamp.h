@@ -75,6 +75,13 @@ struct VampK {
     // this grid's first workgroup in the shared exchange, the exchange's workgroups, and its first
     // trial (0, nwg, 0 for a whole batch or side-by-side epochs)
     int wg_off, nwg_x, row_off;
+    // q0 = Vh r~ of iteration 0 (r~ = sparsity in every row, vamp.py:22-25: one k-vector that
+    // depends on Vh alone), [2k] floats re / im interleaved (bf16x3 engine).  q0_store: workgroup 0
+    // stores row 0 of its GEMM1 result there (a building forward); q0_load (a reuse forward,
+    // amp_vamp_run_reuse): iteration 0 takes GEMM1's result from it instead of building r~ and
+    // running the GEMM.  Two words, each read at its own place in the loop.
+    float* q0;
+    int q0_store, q0_load;
     Const c;
 };
 
@@ -90,6 +97,7 @@ struct VampWs {
     unsigned* pbar;
     DecWG* dwg;
     XState* xs;
+    float* q0;
     size_t bytes;
 };
 
@@ -132,7 +140,8 @@ static VampWs vamp_carve(const amp_dims* d, int k, int max_iter, void* base, int
     w.pparts = cv.take<Partial>((size_t)max_iter * nwg);     // granules carry generation tags
     w.dwg = cv.take<DecWG>((size_t)2 * nwg);              // 256 B of granules per workgroup
     w.xs = cv.take<XState>(1);
-    w.bytes = cv.off;
+    w.q0 = cv.take<float>((size_t)2 * k);                 // iteration 0's q = Vh r~ (VampK.q0), last: the
+    w.bytes = cv.off;                                     // offsets above stay as they were
     return w;
 }
 

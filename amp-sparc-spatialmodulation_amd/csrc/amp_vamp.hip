@@ -530,6 +530,8 @@ static int vamp_setup(const amp_dims* d, const amp_constellation* c, const amp_v
     P.wg_off = 0;
     P.nwg_x = P.nwg;
     P.row_off = 0;
+    P.q0 = w.q0;
+    P.q0_store = P.q0_load = 0;
     return AMP_OK;
 }
 
@@ -600,7 +602,8 @@ static int vamp_prepare_impl(const VampK& P, const amp_vamp_args* a, hipStream_t
 }
 
 // Persistent engine: ONE launch builds the 16x16x4-packed operators (Vh, V), the y~ operator
-// s Uh and zeroes the barrier words; the Tracker's initial state and the iteration-0 scalars
+// s Uh and zeroes the barrier words (a reuse forward, below, has no such launch: the operators stand
+// and the y~ launch zeroes the words); the Tracker's initial state and the iteration-0 scalars
 // are formed inside vamp_persist.  y~ = (s Uh) y: on the fp16x2 engine inside vamp_persist's
 // prologue (n == 2N; AMP_YTIL_IN_KERNEL=0 keeps the separate gemm_store launch), on the other
 // arithmetics from gemm_store (the f32 engine can form it in-kernel with AMP_YTIL_IN_KERNEL=1: ~20
@@ -625,7 +628,7 @@ static bool ytil_x3_env() {
 }
 bool ytil_x3_fits(int n, int k);
 int ytil_x3_launch(const float* y, int n, int rows, const void* wq, float* ytil, int k, hipStream_t st,
-                   int rows_per_op = 0, long long wq_stride = 0);
+                   int rows_per_op = 0, long long wq_stride = 0, unsigned* zero = nullptr, int nzero = 0);
 
 // Side-by-side epochs with a channel each (P.wch != 0): every epoch's split-precision operators
 // (Vh, V, s Uh) from its own U / s / Vh (a->U + e * ch.U, ...), then y~ per epoch.
@@ -656,10 +659,20 @@ static int vamp_persist_prepare_ch(VampK& P, const amp_vamp_args* a, const Epoch
     return ytil_x3_launch((const float*)a->y, P.n, P.B * P.E, P.Wq0, P.ytil, P.k, st, P.B, q0);
 }
 
-static int vamp_persist_prepare(VampK& P, const amp_vamp_args* a, hipStream_t st, const EpochChannels* ch = nullptr) {
+// Diagnostic tallies of the prepares above vamp_persist (amp_vamp_debug_prepare_counts): [0] those
+// that packed the operators, [1] reuse prepares (y~ alone).  Results never depend on them.
+static std::atomic<unsigned long long> g_prepare_counts[2];
+
+// reuse (amp_vamp_run_reuse and its siblings): the caller states that this workspace's packed
+// operators (Wx1, Wx2, Wq0) and q0 are those of the previous forward on it — same dims, k, GEMM
+// arithmetic and U / s / Vh contents.  Honoured on the single-channel bf16x3 path with the y~
+// launch of its own (the only path that stores q0); every other path packs as always.
+static int vamp_persist_prepare(VampK& P, const amp_vamp_args* a, hipStream_t st, const EpochChannels* ch = nullptr,
+                                bool reuse = false) {
     static std::atomic<unsigned> gen{0};
     P.gen = ++gen;
     if (ch && P.wch) {
+        ++g_prepare_counts[0];
         P.ytil_in_kernel = 0;
         return vamp_persist_prepare_ch(P, a, *ch, st);
     }
@@ -670,6 +683,16 @@ static int vamp_persist_prepare(VampK& P, const amp_vamp_args* a, hipStream_t st
         P.ytil_in_kernel = (!P.x3 && env == 1 && vamp_persist_ytil_in_kernel(P)) ? 1 : 0;
     const bool yk = P.ytil_in_kernel != 0;
     const bool yx3 = !yk && (P.x3 == 1 || P.x3 == 3) && ytil_x3_env() && ytil_x3_fits(P.n, P.k);
+    if (yx3 && P.x3 == 1 && P.E == 1) {
+        P.q0_store = reuse ? 0 : 1;
+        P.q0_load = reuse ? 1 : 0;
+        if (reuse) {
+            // the operators and q0 stand: y~ alone, its first workgroup clearing the barrier words
+            // that the pack launch clears on a building forward
+            ++g_prepare_counts[1];
+            return ytil_x3_launch((const float*)a->y, P.n, P.B, P.Wq0, P.ytil, P.k, st, 0, 0, P.pbar, PBAR_WORDS);
+        }
+    }
     CWeightJob j[3];
     if (P.x3) {
         const int pk = P.x3 == 3 ? WPACKI8 : P.x3 == 2 ? WPACKH2 : WPACKX3;
@@ -689,6 +712,7 @@ static int vamp_persist_prepare(VampK& P, const amp_vamp_args* a, hipStream_t st
            : yx3 ? CWeightJob{(const float2*)a->U, 1, P.k, 1, P.s, P.k, P.n, (float*)P.Wq0, P.n, P.k, WPACKX3}
            : yk ? CWeightJob{(const float2*)a->U, 1, P.k, 1, P.s, P.k, P.n, (float*)P.Wq0, 2 * P.n, 2 * P.k, WPACK16}
                 : CWeightJob{(const float2*)a->U, 1, P.k, 1, P.s, P.k, P.n, (float*)P.Wt0, P.kap0, P.ncp0, WPACK32};
+    ++g_prepare_counts[0];
     int rc = build_cweights(j, 3, P.pbar, PBAR_WORDS, st);
     if (rc || yk) return rc;
     if (yx3) return ytil_x3_launch((const float*)a->y, P.n, P.B * P.E, P.Wq0, P.ytil, P.k, st);
@@ -767,8 +791,8 @@ int amp_vamp_run_sharded(const amp_dims* d, const amp_constellation* c, const am
 // GEMM2 + r, partial published, barrier passed, scalars ready, denoiser done, vamp_advance started; then per
 // workgroup [nwg * max_iter * 10 + 2 * wg] = s_memtime / s_memrealtime at kernel start and
 // [nwg * max_iter * 10 + 2 * nwg + 2 * wg] the same pair at its end (trace: 4 nwg more words).
-int amp_vamp_persist_trace(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* trace,
-                           void* stream) {
+int amp_vamp_persist_trace_reuse(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* trace,
+                                 int32_t reuse, void* stream) {
     VampK P;
     Const64 c64;
     int rc = vamp_setup(d, c, a, P, c64);
@@ -776,10 +800,22 @@ int amp_vamp_persist_trace(const amp_dims* d, const amp_constellation* c, const 
     const int ncu = device_cu_count();
     AMP_REQUIRE(trace && vamp_persist_eligible(d, a->k, ncu), "amp_vamp_persist_trace: not eligible / null trace");
     hipStream_t st = (hipStream_t)stream;
-    rc = vamp_persist_prepare(P, a, st);
+    rc = vamp_persist_prepare(P, a, st, nullptr, reuse != 0);
     if (rc) return rc;
     P.trace = (unsigned long long*)trace;
     return vamp_persist_launch(P, c64, DecConst{}, st, ncu);
+}
+
+int amp_vamp_persist_trace(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* trace,
+                           void* stream) {
+    return amp_vamp_persist_trace_reuse(d, c, a, trace, 0, stream);
+}
+
+int amp_vamp_debug_prepare_counts(uint64_t* out) {
+    if (!out) return AMP_E_ARG;
+    out[0] = g_prepare_counts[0].load();
+    out[1] = g_prepare_counts[1].load();
+    return AMP_OK;
 }
 
 int amp_vamp_select_gemm(const amp_dims* d, int32_t k, int32_t gemm) {
@@ -830,7 +866,8 @@ int amp_vamp_finalize(const amp_dims* d, const amp_constellation* c, const amp_v
     return vamp_finalize_impl(P, (hipStream_t)stream);
 }
 
-int amp_vamp_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* stream) {
+int amp_vamp_run_reuse(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, int32_t reuse,
+                       void* stream) {
     VampK P;
     Const64 c64;
     int rc = vamp_setup(d, c, a, P, c64);
@@ -844,7 +881,7 @@ int amp_vamp_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_a
                 "amp_vamp_run: persistent engine needs k == N in {64, 128, 256}, M <= 64 and ceil(B/16) = %d <= "
                 "%d CUs", cdiv(d->B, PBM), ncu);
     if (a->engine == AMP_ENGINE_PERSISTENT || (a->engine == AMP_ENGINE_AUTO && elig)) {
-        rc = vamp_persist_prepare(P, a, st);
+        rc = vamp_persist_prepare(P, a, st, nullptr, reuse != 0);
         if (rc) return rc;
         return vamp_persist_launch(P, c64, DecConst{}, st, ncu);
     }
@@ -857,8 +894,12 @@ int amp_vamp_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_a
     return vamp_finalize_impl(P, st);
 }
 
-int amp_vamp_detect_count(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
-                          const amp_vamp_decide_args* dec, void* stream) {
+int amp_vamp_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* stream) {
+    return amp_vamp_run_reuse(d, c, a, 0, stream);
+}
+
+int amp_vamp_detect_count_reuse(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
+                                const amp_vamp_decide_args* dec, int32_t reuse, void* stream) {
     VampK P;
     Const64 c64;
     int rc = vamp_setup(d, c, a, P, c64);
@@ -871,7 +912,7 @@ int amp_vamp_detect_count(const amp_dims* d, const amp_constellation* c, const a
                 "amp_vamp_detect_count: needs the persistent engine (k == N in {64, 128, 256}, M <= 64, "
                 "ceil(B/16) = %d <= %d CUs)", cdiv(d->B, PBM), ncu);
     hipStream_t st = (hipStream_t)stream;
-    rc = vamp_persist_prepare(P, a, st);
+    rc = vamp_persist_prepare(P, a, st, nullptr, reuse != 0);
     if (rc) return rc;
     P.dec_on = 1;
     P.ibits = dec->ibits_trunc;
@@ -881,6 +922,11 @@ int amp_vamp_detect_count(const amp_dims* d, const amp_constellation* c, const a
     P.counts = (amp_counts*)dec->counts;
     P.host_rec = P.fold_in ? (unsigned char*)dec->host_record : nullptr;
     return vamp_persist_launch(P, c64, to_decconst(c), st, ncu);
+}
+
+int amp_vamp_detect_count(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
+                          const amp_vamp_decide_args* dec, void* stream) {
+    return amp_vamp_detect_count_reuse(d, c, a, dec, 0, stream);
 }
 
 int amp_vamp_max_epochs(const amp_dims* d, int32_t k) {

@@ -397,6 +397,27 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
         stamp(t, 0);
         const float* vprev = lds + ((t & 1) ? Y.offV0 : Y.offV1);
         float* vnew = lds + ((t & 1) ? Y.offV1 : Y.offV0);
+        f32x4 acc[NT];
+        f32x4 cr[NC], ci[NC];
+        // Iteration 0 of a reuse forward (bf16x3 only; wave-uniform): r~ = sparsity in every valid
+        // row, so q = Vh r~ is the one k-vector a building forward left in P.q0 — no r~ planes and
+        // no GEMM1.  An MFMA output row depends on its own A row alone: every valid row's q is the
+        // stored vector bit for bit, and a padded row's (a zero A row) is 0.  Tested once, here,
+        // and off the hot path, so that nothing of it is live in iterations 1 ...
+        if (__builtin_expect(X3 && !H2 && !I8 && t == 0 && P.q0_load != 0, 0)) {
+            stamp(t, 1);
+            const int lnq = pl_opaque(lane);   // (addresses formed here, not hoisted)
+#pragma unroll
+            for (int t2 = 0; t2 < NC; ++t2) {
+                const float2 q = *reinterpret_cast<const float2*>(P.q0 + 2 * (16 * (cc0 + t2) + (lnq & 15)));
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const bool in = 4 * (lnq >> 4) + r < nrows;
+                    cr[t2][r] = in ? q.x : 0.f;
+                    ci[t2][r] = in ? q.y : 0.f;
+                }
+            }
+        } else {   // (steps 1 and 2's GEMM, indented as the rest of the loop body)
         // 1. A <- r~ (vamp.py:91; t = 0: dxdr 0, normScalar 1)
         if constexpr (H2 || I8) {
             // r~ rows in registers (item e: row e % PBM == tid % PBM, 8 complex values), the
@@ -484,8 +505,6 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
         __syncthreads();
         stamp(t, 1);
         // 2. q = Vh r~ ; w = scale (y~ + vr q) - q  -> A   (vamp.py:67-72)
-        f32x4 acc[NT];
-        f32x4 cr[NC], ci[NC];
         if constexpr (I8) {
             float rowf[4];
 #pragma unroll
@@ -493,10 +512,21 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
             gemm_i8<NC, G3 / 2>(sB, ldb, Wx1, N, cc0, rowf, cr, ci);   // 64-deep groups: N / 64
         } else if constexpr (H2)
             gemm_h2<NC, G3>(sP, ldx, Wx1, cc0, cr, ci);
-        else if constexpr (X3)
+        else if constexpr (X3) {
             gemm_x3<NC, G3, X3R, X3PIN, true>(sP, ldx, Wx1, cc0, cr, ci);
-        else
+            // a building forward leaves q0 for the reuse forwards that follow it: row 0 (always a
+            // valid trial) of workgroup 0, lanes 0-15 of every wave
+            if (__builtin_expect(t == 0 && P.q0_store != 0 && wg == 0, 0)) {
+                const int lns = pl_opaque(lane);   // (addresses formed here, not hoisted)
+                if (lns < 16) {
+#pragma unroll
+                    for (int t2 = 0; t2 < NC; ++t2)
+                        *reinterpret_cast<float2*>(P.q0 + 2 * (16 * (cc0 + t2) + lns)) = make_float2(cr[t2][0], ci[t2][0]);
+                }
+            }
+        } else
             gemm16<NT, NT * NWV>(sA, lda, P.Wq1, ct0, acc);   // G = 2N / 16 = NT * NWV
+        }
         float hsc[4];                                 // H2: 2^-(e_row + H2_EX) of this lane's rows
         int hew[4];                                   // H2 / I8: the w rows' exponents
         if constexpr (H2 || I8) {

@@ -42,13 +42,21 @@ namespace amp {
 // gemm_store launch (47.7 us per cfg4 step at 0.56 of the f32 peak, profiles/r04_cfg4_vamp_x3.txt).
 // rows_per_op / wq_stride: side-by-side epochs with a channel each use the operator of their
 // epoch, wq + (row / rows_per_op) * wq_stride bytes (rows_per_op a multiple of PBM).
+// zero / nzero: words the launch's first workgroup clears (null: none) — vamp_persist's barrier
+// words on a reuse forward, which has no operator-pack launch to clear them (amp_vamp.hip).
+__device__ __forceinline__ void ytil_zero_words(unsigned* zero, int nzero) {
+    if (zero && blockIdx.x == 0 && blockIdx.y == 0)
+        for (int i = threadIdx.x; i < nzero; i += blockDim.x) zero[i] = 0u;
+}
+
 template <int NC, int G, int NWV = 4>
 __global__ __launch_bounds__(64 * NWV, 1) void ytil_x3_kernel(const float* __restrict__ y, int rows, const void* wq,
                                                                float* __restrict__ ytil, int k, int rows_per_op,
-                                                               long long wq_stride) {
+                                                               long long wq_stride, unsigned* zero, int nzero) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     unsigned short* sP = reinterpret_cast<unsigned short*>(lds);
     constexpr int n = 32 * G;
+    ytil_zero_words(zero, nzero);
     const int ldx = pl_ldx(n);
     const int row0 = blockIdx.x * PBM;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -164,9 +172,10 @@ __device__ __forceinline__ void x3_rows2(const unsigned short* sP0, const unsign
 template <int GH, int NH>
 __global__ __launch_bounds__(512, 1) void ytil_x3_r2_kernel(const float* __restrict__ y, int rows, const void* wq,
                                                              float* __restrict__ ytil, int k, int rows_per_op,
-                                                             long long wq_stride) {
+                                                             long long wq_stride, unsigned* zero, int nzero) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     unsigned short* sP0 = reinterpret_cast<unsigned short*>(lds);
+    ytil_zero_words(zero, nzero);
     constexpr int KS = 32 * GH, n = KS * NH, G = GH * NH;
     const int ldx = pl_ldx(KS);
     unsigned short* sP1 = sP0 + 6 * 16 * ldx;
@@ -226,7 +235,7 @@ __global__ __launch_bounds__(512, 1) void ytil_x3_r2_kernel(const float* __restr
 }
 
 static int ytil_x3_r2_launch(const float* y, int rows, const void* wq, float* ytil, int k, int rows_per_op,
-                             long long wq_stride, hipStream_t st) {
+                             long long wq_stride, unsigned* zero, int nzero, hipStream_t st) {
     const void* fn = (const void*)ytil_x3_r2_kernel<8, 2>;
     const size_t lds = (size_t)2 * 6 * 16 * pl_ldx(256) * 2;
     static int attr = -1;
@@ -239,7 +248,7 @@ static int ytil_x3_r2_launch(const float* y, int rows, const void* wq, float* yt
         attr = 1;
     }
     hipLaunchKernelGGL((ytil_x3_r2_kernel<8, 2>), dim3(cdiv(rows, 32), 2), dim3(512), lds, st, y, rows, wq, ytil, k,
-                       rows_per_op, wq_stride);
+                       rows_per_op, wq_stride, zero, nzero);
     AMP_LAUNCH_CHECK("ytil_x3_r2");
     return AMP_OK;
 }
@@ -253,7 +262,7 @@ static bool ytil_r2_env() {
 
 template <int NC, int G, int NWV = 4>
 static int ytil_x3_launch_t(const float* y, int rows, const void* wq, float* ytil, int k, int rows_per_op,
-                            long long wq_stride, hipStream_t st) {
+                            long long wq_stride, unsigned* zero, int nzero, hipStream_t st) {
     const void* fn = (const void*)ytil_x3_kernel<NC, G, NWV>;
     const size_t lds = (size_t)6 * PBM * pl_ldx(32 * G) * 2;
     static int attr = -1;   // once per instantiation (single-threaded host use, like the rest of the ABI)
@@ -266,7 +275,7 @@ static int ytil_x3_launch_t(const float* y, int rows, const void* wq, float* yti
         attr = 1;
     }
     hipLaunchKernelGGL((ytil_x3_kernel<NC, G, NWV>), dim3(cdiv(rows, PBM)), dim3(64 * NWV), lds, st, y, rows, wq, ytil, k,
-                       rows_per_op, wq_stride);
+                       rows_per_op, wq_stride, zero, nzero);
     AMP_LAUNCH_CHECK("ytil_x3");
     return AMP_OK;
 }
@@ -275,17 +284,17 @@ static int ytil_x3_launch_t(const float* y, int rows, const void* wq, float* yti
 bool ytil_x3_fits(int n, int k) { return n == 2 * k && (k == 64 || k == 128 || k == 256); }
 
 int ytil_x3_launch(const float* y, int n, int rows, const void* wq, float* ytil, int k, hipStream_t st,
-                   int rows_per_op, long long wq_stride) {
+                   int rows_per_op, long long wq_stride, unsigned* zero, int nzero) {
     if (rows_per_op <= 0) rows_per_op = rows;   // one operator for every row
     AMP_REQUIRE(rows_per_op % PBM == 0 || rows_per_op >= rows, "ytil_x3: rows per operator %d", rows_per_op);
     switch (k) {
-    case 64: return ytil_x3_launch_t<1, 4>(y, rows, wq, ytil, k, rows_per_op, wq_stride, st);
-    case 128: return ytil_x3_launch_t<2, 8>(y, rows, wq, ytil, k, rows_per_op, wq_stride, st);
+    case 64: return ytil_x3_launch_t<1, 4>(y, rows, wq, ytil, k, rows_per_op, wq_stride, zero, nzero, st);
+    case 128: return ytil_x3_launch_t<2, 8>(y, rows, wq, ytil, k, rows_per_op, wq_stride, zero, nzero, st);
     case 256:   // 32 trials x half the outputs per workgroup (every operator group feeds two row
                 // tiles); else eight waves of 16 trials, as in the engine
         if (ytil_r2_env() && (rows_per_op % 32 == 0 || rows_per_op >= rows))
-            return ytil_x3_r2_launch(y, rows, wq, ytil, k, rows_per_op, wq_stride, st);
-        return ytil_x3_launch_t<2, 16, 8>(y, rows, wq, ytil, k, rows_per_op, wq_stride, st);
+            return ytil_x3_r2_launch(y, rows, wq, ytil, k, rows_per_op, wq_stride, zero, nzero, st);
+        return ytil_x3_launch_t<2, 16, 8>(y, rows, wq, ytil, k, rows_per_op, wq_stride, zero, nzero, st);
     default: break;
     }
     set_error("ytil_x3: n = %d / k = %d not supported", n, k);

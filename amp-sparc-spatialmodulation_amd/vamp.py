@@ -51,6 +51,46 @@ class _Buffers:
         return self
 
 
+class _OperatorReuse:
+    """Whether a forward may tell the library that the workspace still holds the previous
+    forward's packed operators and q0 (amp_sparc.h, amp_vamp_run_reuse): the reference draws a
+    channel every `res` epochs and runs `res` forwards on it (vamp_model.py:55-61), and
+    Model.simulate hands those forwards the same U, s, Vh tensors.
+
+    The record of the last forward that returned holds STRONG references to the caller's U, s, Vh
+    objects (a freed channel's address could otherwise be handed to a new one), their `_version`
+    counters, the shape / engine / arithmetic key and the workspace tensor.  begin() answers 1 only
+    when all of them are unchanged, and drops the record until commit(): a forward that raises
+    leaves none.  Nothing derived from y, x or the labels is ever kept."""
+
+    def __init__(self):
+        self._last = None
+        self._cand = None
+
+    def clear(self) -> None:
+        self._last = self._cand = None
+
+    @staticmethod
+    def _versions(*ts):
+        try:
+            return tuple(int(t._version) for t in ts)
+        except Exception:   # noqa: BLE001 — a tensor without a version counter: never reused
+            return None
+
+    def begin(self, U, s, Vh, key, ws) -> int:
+        last, self._last = self._last, None
+        ver = self._versions(U, s, Vh)
+        self._cand = None if ver is None else (U, s, Vh, ver, key, ws)
+        if last is None or self._cand is None:
+            return 0
+        same = (last[0] is U and last[1] is s and last[2] is Vh and last[3] == ver and last[4] == key
+                and last[5] is ws)
+        return 1 if same else 0
+
+    def commit(self) -> None:
+        self._last, self._cand = self._cand, None
+
+
 class Tracker:
     """Device state of one VAMP forward (vamp.py:12-28): r, xmmse, var and the workspace
     holding the expanded V/Vh/U weights, y~ and the per-iteration scalar record."""
@@ -332,7 +372,20 @@ class VAMP(LazyResult, nn.Module):
         self.layers = nn.ModuleList([VAMPLayer(config, i) for i in range(config.N_Layers)])
         self.L = Loss(config)
         self._bufs = _Buffers()
+        self._ops = _OperatorReuse()
         self.last = None
+
+    def _run_reusing(self, T: Tracker, U, s, Vh, call, what: str) -> int:
+        """call(reuse) -> status code, with the reuse flag _OperatorReuse allows for this forward
+        on self._bufs' workspace: same channel objects and versions, dims, k, iterations, engine,
+        gemm and workspace as the last forward that returned.  Returns the flag it passed."""
+        d = T.dims
+        key = (tuple(getattr(d, f) for f, _ in d._fields_), T.k, self.config.N_Layers, self.engine, self.gemm,
+               str(T.y.device))
+        reuse = self._ops.begin(U, s, Vh, key, T.buf.ws)
+        nat.check(call(reuse), what)
+        self._ops.commit()
+        return reuse
 
     def detect(self, U, s, Vh, y, SNR: float) -> Tracker:
         """All iterations on the device, asynchronous (no host sync)."""
@@ -340,8 +393,9 @@ class VAMP(LazyResult, nn.Module):
             T = Tracker(U, s, Vh, y, None, self.E / SNR, self.sparsity, self.config, self._bufs)
             T.args.engine = self.engine
             T.args.gemm = self.gemm
-            nat.check(nat.lib().amp_vamp_run(C.byref(T.dims), C.byref(T.const), C.byref(T.args), T.stream),
-                      'amp_vamp_run')
+            lib = nat.lib()
+            self._run_reusing(T, U, s, Vh, lambda reuse: lib.amp_vamp_run_reuse(
+                C.byref(T.dims), C.byref(T.const), C.byref(T.args), reuse, T.stream), 'amp_vamp_run')
         return T
 
     def forward(self, U: torch.Tensor, s: torch.Tensor, Vh: torch.Tensor, y: torch.Tensor, SNR: float,
@@ -370,10 +424,12 @@ class VAMP(LazyResult, nn.Module):
             # forward + decision on T.r (vamp.py:187) + counters in one launch sequence
             dec = self.L.decide_args(x, symbols, indices, out=res[64:])
             dec.host_record = None if nat.fold_launch() else host.data_ptr()   # status + counters written there
-            nat.check(lib.amp_vamp_detect_count(C.byref(T.dims), C.byref(T.const), C.byref(T.args), C.byref(dec),
-                                                 T.stream), 'amp_vamp_detect_count')
+            self._run_reusing(T, U, s, Vh, lambda reuse: lib.amp_vamp_detect_count_reuse(
+                C.byref(T.dims), C.byref(T.const), C.byref(T.args), C.byref(dec), reuse, T.stream),
+                'amp_vamp_detect_count')
         else:
-            nat.check(lib.amp_vamp_run(C.byref(T.dims), C.byref(T.const), C.byref(T.args), T.stream), 'amp_vamp_run')
+            self._run_reusing(T, U, s, Vh, lambda reuse: lib.amp_vamp_run_reuse(
+                C.byref(T.dims), C.byref(T.const), C.byref(T.args), reuse, T.stream), 'amp_vamp_run')
             # decision on T.r (vamp.py:187); counters land next to the status record
             self.L.device_counts(T.buf.r, T.buf.xmmse, x, symbols, indices, out=res[64:])
         persistent = lib.amp_vamp_select_engine(C.byref(T.dims), T.k, self.engine) == nat.ENGINE_PERSISTENT
@@ -385,7 +441,9 @@ class VAMP(LazyResult, nn.Module):
     def _rescue_forward(self, U, s, Vh, y, SNR, x, symbols, indices):
         """One forward on the launch engine (three launches per iteration: no grid-wide
         exchange inside a kernel), synchronously, into buffers of its own: the rescue of a
-        persistent launch whose grid was lost (LazyResult._check_grid).  Returns (status, counts)."""
+        persistent launch whose grid was lost (LazyResult._check_grid).  Returns (status, counts).
+        The next forward packs its operators again."""
+        self._ops.clear()
         with torch.cuda.device(y.device):
             if getattr(self, '_rescue_bufs', None) is None:
                 self._rescue_bufs = _Buffers()
@@ -440,6 +498,7 @@ class VAMP(LazyResult, nn.Module):
         if not (E == len(xs) == len(symbols) == len(indices)) or E < 1:
             raise ValueError('forward_epochs: ys, xs, symbols and indices must hold the same number (>= 1) of epochs')
         dev = ys[0].device
+        self._ops.clear()
         with torch.cuda.device(dev):
             return self._forward_epochs(U, s, Vh, ys, SNR, xs, symbols, indices, E, dev)
 
@@ -559,6 +618,7 @@ class VAMP(LazyResult, nn.Module):
             raise ValueError('forward_trials runs on the launch engine (the persistent engine has no '
                              'independent-trial form)')
         dev = ys[0].device
+        self._ops.clear()
         with torch.cuda.device(dev):
             cfg = self.config
             n, k, N = U.shape[-2], U.shape[-1], Vh.shape[-1]
@@ -726,6 +786,7 @@ class ShardedVAMP(ShardHook, VAMP):
         self._shard_init(group)
 
     def _forward(self, U, s, Vh, y, SNR, x, symbols, indices) -> Loss:
+        self._ops.clear()
         cfg = self.config
         B = cfg.B
         b0, b1 = self.shard()

@@ -193,6 +193,35 @@ typedef struct amp_vamp_decide_args {
 } amp_vamp_decide_args;
 int amp_vamp_detect_count(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
                           const amp_vamp_decide_args* dec, void* stream);
+/* ---- Operator reuse across forwards on one channel ----
+ * Model.simulate draws a channel only every `res` epochs and runs `res` forwards on it
+ * (vamp_model.py:55-61), so what a forward derives from (U, s, Vh) alone need not be formed again:
+ * the packed operators Vh, V and s U^H in the workspace, and q0 = Vh r~ of iteration 0 (the
+ * Tracker starts every trial at r~ = sparsity, vamp.py:22-25, so that product is one k-vector).
+ * The siblings below take `reuse`:
+ *   reuse == 0  the entry point without the suffix, exactly (a "building" forward: it packs the
+ *               operators and, on the path named below, also leaves q0 in the workspace);
+ *   reuse != 0  the CALLER states that the previous forward on this workspace (a->ws) was a
+ *               building or reuse forward through one of these entry points that returned AMP_OK,
+ *               with the same dims, k, max_iter, a->gemm and engine selection, and the same U / s /
+ *               Vh CONTENTS, and that nothing else has written the workspace since.  The forward
+ *               then skips the operator pack launch and iteration 0's r~ build and first GEMM: two
+ *               launches (y~, vamp_persist) instead of three.  a->U and a->Vh are not read; a->s is.
+ * The library keeps no record of channels and cannot check the statement: a wrong one gives wrong
+ * results without an error.  y~ and everything else that depends on y, x, sym or idx is formed on
+ * every forward.  The results of a reuse forward equal a building forward's bit for bit.
+ * Reuse is honoured only where the persistent engine runs the bf16x3 arithmetic (AMP_GEMM_AUTO /
+ * AMP_GEMM_X3 where it fits) with n == 2 k; on every other path (launch engine, f32 / fp16x2 /
+ * int8x4 arithmetic) the flag is ignored and the forward builds. */
+int amp_vamp_run_reuse(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, int32_t reuse,
+                       void* stream);
+int amp_vamp_detect_count_reuse(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
+                                const amp_vamp_decide_args* dec, int32_t reuse, void* stream);
+int amp_vamp_persist_trace_reuse(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* trace,
+                                 int32_t reuse, void* stream);
+/* Diagnostic: out[0] = persistent-engine prepares of this process that packed the operators,
+ * out[1] = those that reused them (tests read it to see that the flag reached the library). */
+int amp_vamp_debug_prepare_counts(uint64_t* out);
 /* `epochs` independent forwards of d->B trials each that share ONE channel (U, s, Vh) — the
  * epochs of one `res` block of Model.simulate (vamp_model.py:55-61: the channel is redrawn only
  * when i % res == 0) — side by side in one persistent launch.  Each epoch keeps its own

@@ -2,7 +2,9 @@
 """Phase timing of the persistent engines (amp_vamp_persist_trace / amp_scamp_persist_trace): per
 iteration and workgroup s_memtime stamps -> median cycles per phase, barrier skew across workgroups.
 
-  python tools/trace_persist.py [--config cfg4] [--ebn0 8] [--gemm auto|x3|f32|h2|i8]
+  python tools/trace_persist.py [--config cfg4] [--ebn0 8] [--gemm auto|x3|f32|h2|i8] [--reuse]
+--reuse traces a reuse forward (amp_vamp_persist_trace_reuse: the operators and q0 of the forwards
+before it stand); iteration 0's phases are printed on their own either way.
   python tools/trace_persist.py --config cfg3        (SCAMP, tools/configs_bench.py's cfg3 inputs)
 """
 import argparse
@@ -77,6 +79,8 @@ def main():
     ap.add_argument('--config', default='cfg4')
     ap.add_argument('--ebn0', type=float, default=None)
     ap.add_argument('--gemm', default='auto', choices=['auto', 'x3', 'f32', 'h2', 'i8'])
+    ap.add_argument('--reuse', action='store_true',
+                    help='trace a reuse forward (the detect calls before it leave the operators and q0)')
     args = ap.parse_args()
     if args.config.startswith('cfg3'):
         return scamp_trace(args.config, args.ebn0)
@@ -97,8 +101,10 @@ def main():
     tr = torch.zeros(nwg * iters * STRIDE + 4 * nwg, dtype=torch.int64, device=dev)
     s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s0.record()
-    nat.check(nat.lib().amp_vamp_persist_trace(C.byref(T.dims), C.byref(T.const), C.byref(T.args), nat.dptr(tr),
-                                               T.stream), 'trace')
+    b0 = nat.prepare_counts()
+    nat.check(nat.lib().amp_vamp_persist_trace_reuse(C.byref(T.dims), C.byref(T.const), C.byref(T.args), nat.dptr(tr),
+                                                     1 if args.reuse else 0, T.stream), 'trace')
+    b1 = nat.prepare_counts()
     e0.record()
     torch.cuda.synchronize()
     ms = s0.elapsed_time(e0)
@@ -108,13 +114,16 @@ def main():
     st = st[:, :Tn]
     d = np.diff(st, axis=2)                       # [nwg, T, 8]
     total_cyc = np.median(st[:, -1, -1] - st[:, 0, 0])
-    print(f'T={Tn}  nwg={nwg}  kernel+prepare {ms:.3f} ms (events)  median loop cycles {total_cyc:.0f}')
+    print(f'T={Tn}  nwg={nwg}  kernel+prepare {ms:.3f} ms (events)  median loop cycles {total_cyc:.0f}  '
+          f'prepare: {"reuse" if b1[1] > b0[1] else "building"}')
     per_it = np.median(st[:, 1:, 0] - st[:, :-1, 0]) if Tn > 1 else 0
     print(f'median cycles per iteration {per_it:.0f}')
     for i, name in enumerate(PHASES):
         v = d[:, 1:, i] if Tn > 1 else d[:, :, i]
         print(f'  {name:22s} median {np.median(v):9.0f}  p10 {np.percentile(v, 10):9.0f}  p90 {np.percentile(v, 90):9.0f}'
               f'  ({100 * np.median(v) / per_it:5.1f} %)' if per_it else '')
+    print('iteration 0 (median cycles): ' + '  '.join(f'{name} {np.median(d[:, 0, i]):.0f}'
+                                                       for i, name in enumerate(PHASES[:5])))
     raw = a[:nwg * iters * STRIDE].reshape(nwg, iters, STRIDE).astype(np.int64)[:, 1:Tn]
     if Tn > 1 and np.all(raw[:, :, 9] > 0):   # slot 9: the start of vamp_advance (the scalars' own work)
         print(f'  scalars: gather end -> advance start median {np.median(raw[:, :, 9] - raw[:, :, 6]):.0f}, '
