@@ -223,10 +223,55 @@ __device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast
 // accumulate apart from the ten cross-piece products (<= 2^-8 relative), and the two sums are
 // added once at the end: the f32 rounding of the large running sum then happens 2 times per
 // group instead of 12 (the VAMP engine's GEMM error against float64: DESIGN.md §4 item 5).
-template <int NT, int G, int R = 1, bool PIN = false, bool HL = false>
-__device__ __forceinline__ void gemm_x3(const unsigned short* sP, int ldx, const void* __restrict__ wq, int ct0,
-                                        f32x4 (&cr)[NT], f32x4 (&ci)[NT]) {
-    constexpr int RR = G < R ? G : R;
+// The weight ring is a value the caller owns (X3Ring), so that its fill can be issued a phase ahead
+// of the GEMM that consumes it: x3_ring_fill issues the loads of groups 0 .. RR - 1, gemm_x3_ring
+// consumes a filled ring (slot g % RR holds group g) and, with NEXT, refills the slots its last RR
+// groups free with groups 0 .. RR - 1 of the next GEMM's operator (same NT, G, ct0) — where
+// gemm_x3, which is fill + consume with no next, loads nothing.  Only the time at which loads are
+// issued differs: the MFMA sequence of every output is gemm_x3's.
+constexpr int x3_ring_depth(int G, int R) { return G < R ? G : R; }
+template <int NT, int RR>
+struct X3Ring {
+    u32x4 v[RR][NT][6];
+};
+
+template <int G>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t x3_wrsrc(const void* wq, int ct0) {
+    const int ct0u = __builtin_amdgcn_readfirstlane(ct0);
+    return __builtin_amdgcn_make_buffer_rsrc((char*)const_cast<void*>(wq) + (size_t)ct0u * G * 6 * 1024, (short)0,
+                                             0x7ffffff0, 0x00020000);
+}
+
+// One (tile-major) group of a wave's NT tiles into ring slot d.
+template <int NT, int G, int RR, int T0 = 0, int T1 = NT>
+__device__ __forceinline__ void x3_ring_load(X3Ring<NT, RR>& ring, int d, __amdgpu_buffer_rsrc_t wr, int g) {
+    const int vo = (threadIdx.x & 63) * 16;
+#pragma unroll
+    for (int t = T0; t < T1; ++t)
+#pragma unroll
+        for (int f = 0; f < 6; ++f)
+            ring.v[d][t][f] = __builtin_amdgcn_raw_buffer_load_b128(wr, vo, ((t * G + g) * 6 + f) * 1024, 0);
+}
+
+// T0, T1: tiles T0 .. T1 - 1 only (a fill issued in parts around other work).
+template <int NT, int G, int R = 1, int T0 = 0, int T1 = NT>
+__device__ __forceinline__ void x3_ring_fill(X3Ring<NT, x3_ring_depth(G, R)>& ring, const void* __restrict__ wq, int ct0) {
+    const __amdgpu_buffer_rsrc_t wr = x3_wrsrc<G>(wq, ct0);
+#pragma unroll
+    for (int d = 0; d < x3_ring_depth(G, R); ++d) x3_ring_load<NT, G, x3_ring_depth(G, R), T0, T1>(ring, d, wr, d);
+}
+
+// hook(g): called behind group g's MFMAs, before its ring slot is refilled (the microbenchmark's
+// start-up stamp, tools/ubench/ring_prefill_ubench.hip; the engines pass none).
+struct X3NoHook {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+template <int NT, int G, int R = 1, bool PIN = false, bool HL = false, bool NEXT = false, class Hook = X3NoHook>
+__device__ __forceinline__ void gemm_x3_ring(const unsigned short* sP, int ldx, const void* __restrict__ wq, int ct0,
+                                             X3Ring<NT, x3_ring_depth(G, R)>& ring, f32x4 (&cr)[NT], f32x4 (&ci)[NT],
+                                             const void* __restrict__ wq_next = nullptr, Hook&& hook = Hook()) {
+    constexpr int RR = x3_ring_depth(G, R);
+    static_assert(!NEXT || G % RR == 0, "the next operator's group j lands in slot j % RR");
     constexpr int NL = HL ? NT : 1;
     const int lane = threadIdx.x & 63;
     f32x4 lr[NL], li[NL];
@@ -234,18 +279,7 @@ __device__ __forceinline__ void gemm_x3(const unsigned short* sP, int ldx, const
     for (int t = 0; t < NT; ++t) { cr[t] = f32x4{0.f, 0.f, 0.f, 0.f}; ci[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
     for (int t = 0; t < NL; ++t) { lr[t] = f32x4{0.f, 0.f, 0.f, 0.f}; li[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    const int ct0u = __builtin_amdgcn_readfirstlane(ct0);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        (char*)const_cast<void*>(wq) + (size_t)ct0u * G * 6 * 1024, (short)0, 0x7ffffff0, 0x00020000);
-    const int vo = lane * 16;
-    u32x4 ring[RR][NT][6];
-#pragma unroll
-    for (int d = 0; d < RR; ++d)
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int f = 0; f < 6; ++f)
-                ring[d][t][f] = __builtin_amdgcn_raw_buffer_load_b128(wr, vo, ((t * G + d) * 6 + f) * 1024, 0);
+    const __amdgpu_buffer_rsrc_t wr = x3_wrsrc<G>(wq, ct0);
     // A fragment of group g: row lane & 15, chunk 4 g + (lane >> 4), permuted (pl_col): element
     // 8 ((4 g + q) ^ sw) = ((32 g) ^ s32) + 8 (q ^ (sw & 3)), s32 = 32 (sw >> 2) (one v_xad per g)
     const int ln = pl_opaque(lane);
@@ -279,7 +313,7 @@ __device__ __forceinline__ void gemm_x3(const unsigned short* sP, int ldx, const
         for (int f = 0; f < 3; ++f) na[f] = a[3 + f] ^ sgn;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            const u32x4* w = ring[d][t];
+            const u32x4* w = ring.v[d][t];
             f32x4 gr = cr[t], gi = ci[t];
             f32x4 sr = HL ? lr[HL ? t : 0] : gr, si = HL ? li[HL ? t : 0] : gi;   // the cross-piece sums
 #define AMP_MF(acc, x, y) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(x), as_bf16x8(y), acc, 0, 0, 0)
@@ -305,12 +339,11 @@ __device__ __forceinline__ void gemm_x3(const unsigned short* sP, int ldx, const
             cr[t] = gr; ci[t] = gi;
         }
         if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+        hook(g);
         if (g + RR < G) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int f = 0; f < 6; ++f)
-                    ring[d][t][f] = __builtin_amdgcn_raw_buffer_load_b128(wr, vo, ((t * G + g + RR) * 6 + f) * 1024, 0);
+            x3_ring_load<NT, G>(ring, d, wr, g + RR);
+        } else if constexpr (NEXT) {
+            x3_ring_load<NT, G>(ring, d, x3_wrsrc<G>(wq_next, ct0), g + RR - G);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -318,6 +351,14 @@ __device__ __forceinline__ void gemm_x3(const unsigned short* sP, int ldx, const
 #pragma unroll
         for (int t = 0; t < NT; ++t) { cr[t] += lr[HL ? t : 0]; ci[t] += li[HL ? t : 0]; }
     }
+}
+
+template <int NT, int G, int R = 1, bool PIN = false, bool HL = false>
+__device__ __forceinline__ void gemm_x3(const unsigned short* sP, int ldx, const void* __restrict__ wq, int ct0,
+                                        f32x4 (&cr)[NT], f32x4 (&ci)[NT]) {
+    X3Ring<NT, x3_ring_depth(G, R)> ring;
+    x3_ring_fill<NT, G, R>(ring, wq, ct0);
+    gemm_x3_ring<NT, G, R, PIN, HL>(sP, ldx, wq, ct0, ring, cr, ci);
 }
 
 // ---- split-precision complex GEMM (fp16x2) ----

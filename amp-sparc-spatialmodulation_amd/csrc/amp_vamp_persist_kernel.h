@@ -110,6 +110,9 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // eight waves: no A-fragment prefetch in gemm_x3 (the partner wave covers the LDS reads;
     // 24 registers fewer) when AMP_X3_W8_PIN (A/B builds)
     constexpr bool X3PIN = NWV == 8 && AMP_X3_W8_PIN;
+    // bf16x3: each GEMM's operator ring is filled one phase ahead (x3_ring_fill / gemm_x3_ring)
+    constexpr bool X3PF = X3 && !H2 && !I8;
+    constexpr int PFT = (NC + 1) / 2;          // GEMM1's fill: tiles 0 .. PFT - 1 before the r~ plane build, the rest behind it
 #define c64 (static_cast<const Const64&>(*Dp))
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_flag;
@@ -399,6 +402,13 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
         float* vnew = lds + ((t & 1) ? Y.offV1 : Y.offV0);
         f32x4 acc[NT];
         f32x4 cr[NC], ci[NC];
+        // bf16x3: the operator ring of both GEMMs.  GEMM1's first groups are requested around the
+        // r~ plane build (half the tiles before it, half behind it: all of them before it held every
+        // wave ~800 cycles in the loads' issue, the CU's 96 KB of requests queueing in front of the
+        // build's LDS work); GEMM1 refills the ring with GEMM2's first groups in its last groups, so
+        // they are in flight over GEMM1's tail, the w store and both barriers (the L2 -> CU path is
+        // idle in those phases and the wall of both GEMMs).  Nothing reads the ring after GEMM2.
+        X3Ring<NC, x3_ring_depth(G3, X3R)> wring;
         // Iteration 0 of a reuse forward (bf16x3 only; wave-uniform): r~ = sparsity in every valid
         // row, so q = Vh r~ is the one k-vector a building forward left in P.q0 — no r~ planes and
         // no GEMM1.  An MFMA output row depends on its own A row alone: every valid row's q is the
@@ -417,6 +427,7 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                     ci[t2][r] = in ? q.y : 0.f;
                 }
             }
+            x3_ring_fill<NC, G3, X3R>(wring, Wx2, cc0);   // no GEMM1 to fill GEMM2's ring
         } else {   // (steps 1 and 2's GEMM, indented as the rest of the loop body)
         // 1. A <- r~ (vamp.py:91; t = 0: dxdr 0, normScalar 1)
         if constexpr (H2 || I8) {
@@ -476,6 +487,10 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 }
             }
         } else if constexpr (X3) {
+            if constexpr (X3PF) {
+                x3_ring_fill<NC, G3, X3R, 0, PFT>(wring, Wx1, cc0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             const int tdx = NWV == 8 ? pl_opaque(tid) : tid;   // eight waves: addresses formed here
             for (int e = tdx; e < PBM * (N >> 3); e += PWG) {   // 8 complex values per item
                 // consecutive items walk the 16 rows (row stride 2N + 4 floats): each group of 16
@@ -492,6 +507,10 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                     im[2 * h + 1] = (x.w - cur.dxdr_prev * q.w) * cur.ns_prev;
                 }
                 x3_store8(sP, ldx, row, j0, re, im);
+            }
+            if constexpr (X3PF) {
+                __builtin_amdgcn_sched_barrier(0);
+                x3_ring_fill<NC, G3, X3R, PFT, NC>(wring, Wx1, cc0);
             }
         } else
         for (int e = tid; e < PBM * (twoN >> 2); e += PWG) {
@@ -513,7 +532,7 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
         } else if constexpr (H2)
             gemm_h2<NC, G3>(sP, ldx, Wx1, cc0, cr, ci);
         else if constexpr (X3) {
-            gemm_x3<NC, G3, X3R, X3PIN, true>(sP, ldx, Wx1, cc0, cr, ci);
+            gemm_x3_ring<NC, G3, X3R, X3PIN, true, true>(sP, ldx, Wx1, cc0, wring, cr, ci, Wx2);
             // a building forward leaves q0 for the reuse forwards that follow it: row 0 (always a
             // valid trial) of workgroup 0, lanes 0-15 of every wave
             if (__builtin_expect(t == 0 && P.q0_store != 0 && wg == 0, 0)) {
@@ -689,7 +708,7 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { cr[t2][r] *= hsc[r]; ci[t2][r] *= hsc[r]; }
             }
-            if constexpr (!I8 && !H2) gemm_x3<NC, G3, X3R, X3PIN, true>(sP, ldx, Wx2, cc0, cr, ci);
+            if constexpr (X3PF) gemm_x3_ring<NC, G3, X3R, X3PIN, true>(sP, ldx, Wx2, cc0, wring, cr, ci);
             r_epi(cc0, cr, ci);
         } else {
         gemm16<NT, NT * NWV>(sA, lda, P.Wq2, ct0, acc);
