@@ -148,6 +148,8 @@ SIGNATURES = {
     'amp_vamp_trials_run': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _P]),
     'amp_bamp_trials_workspace_bytes': (C.c_size_t, [_D, _I, _I]),
     'amp_bamp_trials_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _P]),
+    'amp_scamp_trials_workspace_bytes': (C.c_size_t, [_D, _I, _I]),
+    'amp_scamp_trials_run': (C.c_int, [_D, _K, C.POINTER(AmpScampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _P]),
     'amp_bamp_workspace_bytes': (C.c_size_t, [_D, _I]),
     'amp_bamp_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),
     'amp_bamp_prepare': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),

@@ -188,6 +188,48 @@ class SCAMP(LazyResult, nn.Module):
         self.last = T
         return self.L
 
+    def forward_trials(self, W: torch.Tensor, A: torch.Tensor, ys, SNR: float, xs, symbols, indices) -> list:
+        """E independent single-trial detections that share ONE channel (W, A) and one SNR, in one
+        launch sequence (amp_scamp_trials_run) — the epochs of one `res` block of the reference's
+        driver, which runs batch = 1 (scamp_model.py:88, 95).  Each trial is the B = 1 forward of
+        that trial alone: its own max|xi| shift (scamp.py:65), its own allclose(psi) exit and
+        iteration count (scamp.py:105), decided on xmap (scamp.py:107) and counted as Loss at B = 1
+        in generator_mode 'sparc' or 'segmented'.  Returns E Loss objects (in order) that equal E
+        sequential forward() calls on the launch engine; they resolve lazily.  ys / xs / symbols /
+        indices as VAMP.forward_trials.  ValueError unless config.B == 1."""
+        E = self._trials_check(ys, xs, symbols, indices)
+        dev = ys[0].device
+        with torch.cuda.device(dev):
+            cfg = self.config
+            n, N = A.shape[-2], A.shape[-1]
+            Ac = _c64(A, (n, N))
+            Wc = W.reshape(cfg.Lout, cfg.Lin).to(device=dev, dtype=torch.float32).resolve_neg().contiguous()
+            y, x, sym, idx, res, host, dec = self._trials_inputs(ys, xs, symbols, indices, E, n, dev)
+            d, cst = cfg.dims(), cfg.constellation()
+            lib = nat.lib()
+            wsb = lib.amp_scamp_trials_workspace_bytes(C.byref(d), cfg.N_Layers, E)
+            if wsb == 0:
+                raise ValueError('amp_scamp_trials_workspace_bytes: invalid dimensions')
+            ws = nat.WORKSPACE.get(dev, 'scamp_trials', wsb)
+            xmap = torch.empty(E, N, dtype=torch.complex64, device=dev)
+            xm = torch.empty_like(xmap)
+            psi = torch.empty(E, cfg.Lin, dtype=torch.float32, device=dev)
+            a = nat.AmpScampArgs()
+            a.W, a.A, a.y = nat.dptr(Wc, torch.float32, 'W'), nat.dptr(Ac, name='A'), nat.dptr(y, name='y')
+            a.max_iter = cfg.N_Layers
+            a.engine = nat.ENGINE_LAUNCHES
+            a.gemm = nat.GEMM_AUTO
+            a.noise_var = float(self.E / SNR)                                  # scamp.py:98
+            a.xmap, a.xmmse, a.psi = nat.dptr(xmap), nat.dptr(xm), nat.dptr(psi)
+            a.status = nat.dptr(res)
+            a.ws, a.ws_bytes = nat.dptr(ws), ws.numel()
+            nat.check(lib.amp_scamp_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
+                                               nat.stream_ptr(dev)), 'amp_scamp_trials_run')
+            out = self._trials_losses(res, host, E, dev)
+            self._trials_keep = (y, x, sym, idx, Ac, Wc)   # alive until the kernels have read them
+            self.last_trials = (xmap.view(E, 1, N, 1), xm.view(E, 1, N, 1), psi.view(E, 1, cfg.Lin, 1))
+        return out
+
     def _rescue_forward(self, W, A, y, SNR, x, symbol, index):
         """One forward on the launch engine, synchronously, into buffers of its own: the rescue
         of a persistent launch whose grid was lost (vamp.LazyResult._check_grid)."""

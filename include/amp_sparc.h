@@ -476,21 +476,24 @@ int amp_segmented_decide_count(const amp_dims* d, const amp_constellation* c, co
 
 /* ---- Independent-trial batches — `trials` single-trial detections that share ONE channel and one
  *      SNR, in one launch sequence: the reference's own drivers run batch = 1 with res epochs per
- *      channel (vamp_model.py:91, 98; bamp_model.py:89, 96), and generator_mode='segmented' runs
- *      at B = 1 only (loss.py:232).  At B = 1 every batch-global value of the forward is a
- *      per-trial value — var.mean() (vamp.py:85), the max|xi| shift whose float64 underflow decides
- *      which sections turn NaN (vamp.py:112, bamp.py:70), torch.allclose (vamp.py:185,
- *      bamp.py:140) — so trial e here IS the B = 1 forward of trial e alone, with its own iteration
- *      count T_e, and a huge or NaN trial changes no other trial.  A stopped trial is frozen: its
- *      r / xmap, xmmse and var are those of its iteration T_e.
+ *      channel (vamp_model.py:91, 98; bamp_model.py:89, 96; scamp_model.py:88, 95), and
+ *      generator_mode='segmented' runs at B = 1 only (loss.py:232).  At B = 1 every batch-global
+ *      value of the forward is a per-trial value — var.mean() (vamp.py:85), the max|xi| shift whose
+ *      float64 underflow decides which sections turn NaN (vamp.py:112, bamp.py:70, scamp.py:65),
+ *      torch.allclose (vamp.py:185, bamp.py:140, scamp.py:105 on psi) — so trial e here IS the
+ *      B = 1 forward of trial e alone, with its own iteration count T_e, and a huge or NaN trial
+ *      changes no other trial.  A stopped trial is frozen: its r / xmap, xmmse and var (SCAMP: psi)
+ *      are those of its iteration T_e.
  *      d describes ONE trial (d->B == 1).  y, r / xmap, xmmse, var hold the trials' rows back to
- *      back ([trials][len]); a->status -> amp_status[trials] (gemm: AMP_ARITH_F32).  dec (may be
+ *      back ([trials][len]; SCAMP: psi [trials][Lin], W and A shared); a->status ->
+ *      amp_status[trials] (gemm: AMP_ARITH_F32).  dec (may be
  *      NULL: forward only): x / sym / idx hold the trials' rows back to back, counts ->
  *      amp_counts[trials], each trial decided and counted as Loss at B = 1 (Ns = Lin Na,
  *      ibits_trunc = ceil(log2(Lin Na)), flat indices local to the trial; loss.py:67-179) by the
  *      MAP rule (loss.py:282-302) or the segmented rule (loss.py:222-250).  Launch engine, f32
- *      GEMMs, any trials >= 1; AMP_E_ARG for the shapes amp_vamp_run / amp_bamp_run refuse, for
- *      the persistent engine and for BAMP's element-wise denoiser ('random' mode). */
+ *      GEMMs, any trials >= 1; AMP_E_ARG for the shapes amp_vamp_run / amp_bamp_run /
+ *      amp_scamp_run refuse, for the persistent engine and for BAMP's element-wise denoiser
+ *      ('random' mode).  SCAMP decides on xmap (scamp.py:107). */
 #define AMP_RULE_SPARC 0
 #define AMP_RULE_SEGMENTED 1
 typedef struct amp_trials_decide_args {
@@ -509,6 +512,10 @@ int amp_vamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp
 size_t amp_bamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials);
 int amp_bamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
                         const amp_trials_decide_args* dec, int32_t trials, void* stream);
+/* replaces `trials` calls of SCAMP.forward at B = 1 (scamp.py:77-107) + Loss.error_rate */
+size_t amp_scamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials);
+int amp_scamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
+                         const amp_trials_decide_args* dec, int32_t trials, void* stream);
 
 /* ---- Element-wise shrinkage denoisers — replace Shrink (shrink.py:8-166).
  * r: [count] complex64 (is_complex != 0) or float32; cov: cov_vec [count] float32, or

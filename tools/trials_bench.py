@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """Independent-trial batches at the reference's published long-sequence shape
 (Nt=128 Na=8 Nr=24 Lh=3 Lin=20, OOK, generator_mode='segmented': N = 2560, n = 528), the way its
-drivers run it: batch = 1, E = 100 epochs per channel (vamp_model.py:91, 98; bamp_model.py:89, 96).
+drivers run it: batch = 1, E = 100 epochs per channel (vamp_model.py:91, 98; bamp_model.py:89, 96;
+scamp_model.py:88, 95).
 
-Per detector (VAMP, BAMP): the same 100 trials, one channel, once as 100 sequential B = 1
+Per detector (VAMP, BAMP, SCAMP): the same 100 trials, one channel, once as 100 sequential B = 1
 forwards (launch engine) and once as ONE forward_trials call, on the same build and device,
 alternating, after a warm-up of both; there are `reps` timed windows per path, each a whole pass
 over the 100 trials (the grouped path: as many calls as fill half a sequential pass) that ends in
 a device synchronise (the Losses are resolved inside the window: the host
 needs them per epoch).  The results are compared first (T and every counter per trial).
-Writes one JSON line per detector to profiles/trials_bench.jsonl and prints it.
-  python tools/trials_bench.py [E] [reps] [EbN0dB]"""
+Writes one JSON line per detector to profiles/trials_bench.jsonl and prints it; with a list of
+detectors (e.g. `scamp`) only those legs run and the other detectors' recorded lines are kept.
+  python tools/trials_bench.py [E] [reps] [EbN0dB] [vamp,bamp,scamp]"""
 import json
 import os
 import statistics
@@ -28,21 +30,29 @@ from channel import Channel  # noqa: E402
 from config import Config  # noqa: E402
 from data import Data  # noqa: E402
 from loss import counts_to_vector  # noqa: E402
+from scamp import SCAMP  # noqa: E402
 from vamp import VAMP  # noqa: E402
 
 SHAPE = dict(Nt=128, Na=8, Nr=24, Lin=20, Lh=3)
+DETECTORS = ('vamp', 'bamp', 'scamp')
 
 
 def main():
     E = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     EbN0 = float(sys.argv[3]) if len(sys.argv) > 3 else 6.0
+    legs = sys.argv[4].split(',') if len(sys.argv) > 4 else list(DETECTORS)
+    if not legs or any(a not in DETECTORS for a in legs):
+        raise SystemExit(f'trials_bench: detectors are {DETECTORS}')
     if not torch.cuda.is_available():
         raise SystemExit('trials_bench: no ROCm device (a time is measured on the GPU or not at all)')
     dev = torch.device('cuda:0')
     out_path = os.path.join(REPO, 'profiles', 'trials_bench.jsonl')
-    lines = []
-    for algo in ('vamp', 'bamp'):
+    lines = {}
+    if os.path.exists(out_path):
+        with open(out_path) as f:
+            lines = {json.loads(ln)['detector']: ln.strip() for ln in f if ln.strip()}
+    for algo in [a for a in DETECTORS if a in legs]:
         np.random.seed(0)
         torch.manual_seed(0)
         cfg = Config(SHAPE['Nt'], SHAPE['Na'], SHAPE['Nr'], SHAPE['Lin'], SHAPE['Lh'], batch=1,
@@ -62,9 +72,12 @@ def main():
             U, sv, Vh = torch.linalg.svd(A, full_matrices=False)
             chan = (U.to(dev), sv.to(dev), Vh.to(dev))
             det = VAMP(cfg, engine=nat.ENGINE_LAUNCHES)
-        else:
+        elif algo == 'bamp':
             chan = (A.to(dev),)
             det = BAMP(cfg)
+        else:
+            chan = (W.to(dev), A.to(dev))
+            det = SCAMP(cfg, engine=nat.ENGINE_LAUNCHES)
 
         def seq():
             recs = []
@@ -106,9 +119,9 @@ def main():
                    ratio=ms / mg, ideal_ratio=E * float(np.mean(Ts)) / max(Ts),
                    device=torch.cuda.get_device_name(0))
         print(json.dumps(rec))
-        lines.append(json.dumps(rec))
+        lines[algo] = json.dumps(rec)
     with open(out_path, 'w') as f:
-        f.write('\n'.join(lines) + '\n')
+        f.write('\n'.join(lines[a] for a in DETECTORS if a in lines) + '\n')
 
 
 if __name__ == '__main__':
