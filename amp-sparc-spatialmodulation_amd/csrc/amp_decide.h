@@ -161,15 +161,100 @@ __device__ __forceinline__ void decide_section_seg(const DecConst& c, int M, int
 // reference's duplicated 16-QAM point, or near-ties) are compared in float64 with np.argmax's
 // rule; a section with a non-finite input is evaluated entirely in float64.  PF pays where
 // the group is small (few lanes, many positions per lane: the persistent epilogue).
-template <int KK, int G, bool PF, class LD>
+//
+// NARROW (with PF; must be called by all 64 lanes of the wave): pass 1 also keeps, per lane, the
+// largest per-position maximum b1 of v32, its (first) position m1 and the largest maximum b2 over
+// the lane's other positions.  A position whose maximum is below thr holds no candidate, so a lane
+// with b2 < thr has candidates at m1 only (and none at all when b1 < thr).  When that holds for
+// every lane of the wave and no section is non-finite (one ballot: a wave-uniform branch), the
+// candidate count, the first index and the float64 comparison visit position m1 alone: the same
+// candidate set {(m, k): v32 >= thr} in the same order, hence the same decision.  Any other wave
+// runs the passes over every position, as without NARROW.
+template <int KK, int G, bool PF, bool NARROW = false, class LD>
 __device__ __forceinline__ void decide_section(const DecConst& c, int M, int g, const LD& ld, int& bi_out, int& mm_out,
                                                double& se_out) {
+    static_assert(PF || !NARROW, "NARROW is a form of the prefiltered decision");
     constexpr int K = KK;
     constexpr int KU = KUnroll<KK>::value;
     bool full = true;
     float thr = 0.f;
     int ncand = 0, first = 0x7fffffff;
-    if (PF) {
+    if constexpr (PF && NARROW) {
+        float vmax = -INFINITY, xs = 0.f, b1 = -INFINITY, b2 = -INFINITY;
+        int bad = 0, m1 = g < M ? g : 0;   // (a lane with no position, M < G: b1 = -inf, never visited)
+        for (int m = g; m < M; m += G) {
+            float2 xv, xt, xe;
+            ld(m, xv, xt, xe);
+            bad |= !(fabsf(xv.x) <= FLT_MAX && fabsf(xv.y) <= FLT_MAX);
+            xs = fmaxf(xs, fabsf(xv.x) + fabsf(xv.y));
+            float pm = -INFINITY;   // this position's maximum over k (the maximum over all (m, k) is the
+                                    // maximum of these: fmaxf skips a NaN wherever it stands)
+#pragma unroll KU
+            for (int k = 0; k < K; ++k) pm = fmaxf(pm, fmaf(xv.x, c.re32[k], xv.y * c.im32[k]));
+            vmax = fmaxf(vmax, pm);
+            const bool up = pm > b1;
+            b2 = up ? b1 : fmaxf(b2, pm);
+            m1 = up ? m : m1;
+            b1 = up ? pm : b1;
+        }
+        vmax = dec_group_reduce<G>(vmax, [](float a, float b) { return fmaxf(a, b); });
+        xs = dec_group_reduce<G>(xs, [](float a, float b) { return fmaxf(a, b); });
+        bad = dec_group_reduce<G>(bad, [](int a, int b) { return a | b; });
+        thr = vmax - 2.f * (xs * c.amax * 0x1p-20f + 0x1p-126f);
+        if (__builtin_amdgcn_ballot_w64(!bad && b2 < thr) == ~0ull) {   // wave-uniform
+            const bool vis = b1 >= thr;
+            float2 xv, xt, xe;
+            ld(m1, xv, xt, xe);
+#pragma unroll KU
+            for (int k = 0; k < K; ++k) {
+                const bool cand = vis && fmaf(xv.x, c.re32[k], xv.y * c.im32[k]) >= thr;
+                first = (cand && first == 0x7fffffff) ? m1 * K + k : first;
+                ncand += cand ? 1 : 0;
+            }
+            ncand = dec_group_reduce<G>(ncand, [](int a, int b) { return a + b; });
+            first = dec_group_reduce<G>(first, [](int a, int b) { return a < b ? a : b; });
+            int bi = first;
+            if (ncand > 1) {
+                double bv = -INFINITY;
+                bool bn = false;
+                bi = 0x7fffffff;
+                const double xr = (double)xv.x, xi = (double)xv.y;
+#pragma unroll KU
+                for (int k = 0; k < K; ++k) {
+                    if (vis && fmaf(xv.x, c.re32[k], xv.y * c.im32[k]) >= thr) {
+                        const double v = __fma_rn(xr, c.re[k], __dmul_rn(xi, c.im[k]));
+                        const bool vn = v != v;
+                        const int f = m1 * K + k;
+                        if (dec_better(v, f, vn, bv, bi, bn)) { bv = v; bi = f; bn = vn; }
+                    }
+                }
+#pragma unroll
+                for (int o = 1; o < G; o <<= 1) {
+                    const double ov = __shfl_xor(bv, o, 64);
+                    const int oi = __shfl_xor(bi, o, 64);
+                    const bool on = __shfl_xor((int)bn, o, 64) != 0;
+                    if (dec_better(ov, oi, on, bv, bi, bn)) { bv = ov; bi = oi; bn = on; }
+                }
+            }
+            section_tail<KK, G>(c, M, g, ld, bi, bi_out, mm_out, se_out);
+            return;
+        }
+        if (!bad) {
+            for (int m = g; m < M; m += G) {
+                float2 xv, xt, xe;
+                ld(m, xv, xt, xe);
+#pragma unroll KU
+                for (int k = 0; k < K; ++k) {
+                    const bool cand = fmaf(xv.x, c.re32[k], xv.y * c.im32[k]) >= thr;
+                    first = (cand && first == 0x7fffffff) ? m * K + k : first;
+                    ncand += cand ? 1 : 0;
+                }
+            }
+            ncand = dec_group_reduce<G>(ncand, [](int a, int b) { return a + b; });
+            first = dec_group_reduce<G>(first, [](int a, int b) { return a < b ? a : b; });
+        }
+        full = bad != 0;
+    } else if (PF) {
         float vmax = -INFINITY, xs = 0.f;
         int bad = 0;
         for (int m = g; m < M; m += G) {

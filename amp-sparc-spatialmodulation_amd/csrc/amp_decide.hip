@@ -243,6 +243,80 @@ __global__ __launch_bounds__(1024) void map_count_kernel(DecK P) {
     }
 }
 
+// Diagnostic (amp_decide_debug_sections): the fused epilogue's section decision on caller-supplied
+// rows.  As decide_epilogue (amp_decide_fused.h) does it: a workgroup of eight waves holds 16 rows
+// of the decision input, xmmse and the truth in LDS at the engines' row stride, a group of four
+// lanes decides one section with the prefiltered decide_section (NARROW: its narrowed scan), 16
+// sections per wave step; instead of counting, lane 0 of the group stores the section's results.
+constexpr int DBG_WG = 512, DBG_ROWS = 16;
+
+struct DecDbgK {
+    int B, L, M, N, ldr;
+    const float* xmap;
+    const float* xmmse;
+    const float* x;
+    int* bi;
+    int* mm;
+    double* se;
+    DecConst c;
+};
+
+template <int KK, bool NARROW>
+__global__ __launch_bounds__(DBG_WG) void decide_debug_kernel(DecDbgK P) {
+    extern __shared__ __attribute__((aligned(16))) float dbg_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int M = P.M, L = P.L, N = P.N, ldr = P.ldr;
+    const int row0 = blockIdx.x * DBG_ROWS, nrows = min(DBG_ROWS, P.B - row0);
+    float* sR = dbg_lds;
+    float* sX = sR + DBG_ROWS * ldr;
+    float* sT = sX + DBG_ROWS * ldr;
+    for (int e = tid; e < nrows * (N >> 1); e += DBG_WG) {   // float4: two complex entries
+        const int row = e / (N >> 1), c4 = 4 * (e - row * (N >> 1));
+        const size_t go = (size_t)(row0 + row) * 2 * N + c4;
+        *reinterpret_cast<float4*>(sR + row * ldr + c4) = *reinterpret_cast<const float4*>(P.xmap + go);
+        *reinterpret_cast<float4*>(sX + row * ldr + c4) = *reinterpret_cast<const float4*>(P.xmmse + go);
+        *reinterpret_cast<float4*>(sT + row * ldr + c4) = *reinterpret_cast<const float4*>(P.x + go);
+    }
+    __syncthreads();
+    const int S = nrows * L;
+    constexpr int DG = 4;
+    const int g = lane % DG;
+    for (int base = wave * (64 / DG); base < S; base += (DBG_WG / 64) * (64 / DG)) {   // wave-uniform
+        const int ls = base + lane / DG;
+        const bool act = ls < S;
+        const int lsc = act ? ls : S - 1;
+        const int row = lsc / L, l = lsc - row * L;
+        const float* rp = sR + row * ldr + 2 * l * M;
+        const float* xp = sX + row * ldr + 2 * l * M;
+        const float* tp = sT + row * ldr + 2 * l * M;
+        auto ld = [&](int m, float2& xv, float2& xt, float2& xe) {
+            xv = *reinterpret_cast<const float2*>(rp + 2 * m);
+            xe = *reinterpret_cast<const float2*>(xp + 2 * m);
+            xt = *reinterpret_cast<const float2*>(tp + 2 * m);
+        };
+        int bi, mm;
+        double se;
+        decide_section<KK, DG, true, NARROW>(P.c, M, g, ld, bi, mm, se);
+        if (act && g == 0) {
+            const size_t s = (size_t)(row0 + row) * L + l;
+            P.bi[s] = bi;
+            P.mm[s] = mm;
+            P.se[s] = se;
+        }
+    }
+}
+
+template <int KK>
+static hipError_t launch_decide_debug(const DecDbgK& P, bool narrow, hipStream_t st) {
+    const size_t lds = (size_t)3 * DBG_ROWS * P.ldr * sizeof(float);
+    const void* fn = narrow ? (const void*)decide_debug_kernel<KK, true> : (const void*)decide_debug_kernel<KK, false>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    DecDbgK Pc = P;
+    void* args[] = {(void*)&Pc};
+    return hipLaunchKernel(fn, dim3(cdiv(P.B, DBG_ROWS)), dim3(DBG_WG), args, lds, st);
+}
+
 static int decide_nblk(const amp_dims* d) {
     const int G = d->M < 64 ? d->M : 64;
     const int per = (AMP_WG / 64) * (64 / G);
@@ -330,6 +404,39 @@ int amp_map_decide_count_rows(const amp_dims* d, const amp_constellation* c, con
     AMP_REQUIRE(row0 >= 0, "amp_map_decide_count_rows: row0 = %lld", (long long)row0);
     return decide_count(0, d, c, xmap, xmmse, x, sym, idx, ibits_trunc, counts, decisions, ws, ws_bytes, stream,
                         (long long)row0);
+}
+
+int amp_decide_debug_sections(const amp_dims* d, const amp_constellation* c, const void* xmap, const void* xmmse,
+                              const void* x, int32_t narrow, void* decisions, void* mismatch, void* sqerr,
+                              void* stream) {
+    int rc = check_dims(d, c, false);
+    if (rc) return rc;
+    AMP_REQUIRE(xmap && xmmse && x && decisions && mismatch && sqerr, "amp_decide_debug_sections: null pointer argument");
+    AMP_REQUIRE(d->N >= 2 && d->N <= 256 && d->N % 2 == 0 && d->M >= 1 && d->M <= 64 && is_pow2(d->M) &&
+                    d->N == d->L * d->M,
+                "amp_decide_debug_sections: N = %d (even, <= 256), M = %d (a power of two <= 64), L = %d", d->N, d->M,
+                d->L);
+    DecDbgK P;
+    P.B = d->B; P.L = d->L; P.M = d->M; P.N = d->N;
+    P.ldr = 2 * d->N + 8;   // the split-precision engines' row stride (amp_vamp_persist_kernel.h playout)
+    P.xmap = (const float*)xmap; P.xmmse = (const float*)xmmse; P.x = (const float*)x;
+    P.bi = (int*)decisions; P.mm = (int*)mismatch; P.se = (double*)sqerr;
+    P.c = to_decconst(c);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    switch (P.c.K) {
+    case 1: e = launch_decide_debug<1>(P, narrow != 0, st); break;
+    case 2: e = launch_decide_debug<2>(P, narrow != 0, st); break;
+    case 4: e = launch_decide_debug<4>(P, narrow != 0, st); break;
+    case 8: e = launch_decide_debug<8>(P, narrow != 0, st); break;
+    case 16: e = launch_decide_debug<16>(P, narrow != 0, st); break;
+    default: e = launch_decide_debug<64>(P, narrow != 0, st); break;
+    }
+    if (e != hipSuccess) {
+        set_error("amp_decide_debug_sections: %s", hipGetErrorString(e));
+        return AMP_E_LAUNCH;
+    }
+    return AMP_OK;
 }
 
 int amp_segmented_decide_count(const amp_dims* d, const amp_constellation* c, const void* xmap, const void* xmmse,

@@ -23,7 +23,8 @@ namespace amp {
 // dec_fold_gather): the record is published as 13 tagged 16-byte granules of 8 bytes each (sc1
 // write-through stores, like the per-iteration partials, amp_persist.h part_publish) at
 // P.dwg + 256 blockIdx.x bytes; else stored plainly for vamp_decide_fold.
-template <int PWG, int KK, bool PUB = false, class PK>
+// NARROW: decide_section's narrowed candidate scan (amp_decide.h; the same decisions).
+template <int PWG, int KK, bool PUB = false, bool NARROW = false, class PK>
 __device__ __forceinline__ void decide_epilogue(const PK& P, const DecConst& dc, const float* sR, const float* sX, int ldr, int row0,
                                 int lrow0, int nrows, float* sT, void* lab_lds, int lab_cap, void* scr,
                                 unsigned pub_tag = 0) {
@@ -95,7 +96,7 @@ __device__ __forceinline__ void decide_epilogue(const PK& P, const DecConst& dc,
         };
         int bi, mm;
         double se;
-        decide_section<KK, DG, true>(dc, M, g, ld, bi, mm, se);
+        decide_section<KK, DG, true, NARROW>(dc, M, g, ld, bi, mm, se);
         if (act && g == 0) {
             const long long s = (long long)(lrow0 + row) * L + l;
             mism[lsc] = (unsigned char)mm;

@@ -637,6 +637,184 @@ __device__ __forceinline__ void denoise_step_grid2(const P& pol, int base, int n
     }
 }
 
+// denoise_step_grid2's arithmetic on the scaled inputs (ur, ui) of its two sections, for the
+// full-round step below: the posterior mean (xr, xi), the variance and the sections' max logit /
+// max |logit|.  A restatement, operation for operation, and not a function both steps share: the
+// engines that keep denoise_step_grid2 must keep their code objects unchanged.
+template <bool kVar, int R, int PAT, int G>
+__device__ __forceinline__ void grid2_core(const f2v ur, const f2v ui, const GridRegs<R>& Q, f2v& xr_out, f2v& xi_out,
+                                           f2v& var_out, f2v& smax_out, f2v& sabs_out) {
+    constexpr bool FULLG = PAT == GRID_FULL;
+    f2v X[R], Y[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        X[i] = ur * f2splat(Q.re[i]);
+        Y[i] = ui * f2splat(Q.im[i]);
+    }
+    f2v mx, my, lmx, smax, sabs;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        float ax = -FLT_MAX, nx = FLT_MAX, ay = -FLT_MAX, ny = FLT_MAX;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            ax = fmaxf(ax, X[i][u]); nx = fminf(nx, X[i][u]);
+            ay = fmaxf(ay, Y[i][u]); ny = fminf(ny, Y[i][u]);
+        }
+        mx[u] = ax; my[u] = ay;
+        lmx[u] = ax + ay;                          // max logit of the position (a corner)
+        smax[u] = group_fmax_c<G>(lmx[u]);
+        sabs[u] = group_fmax_c<G>(fmaxf(lmx[u], -(nx + ny)));   // max |logit|
+    }
+    const f2v l2e = f2splat(AMP_LOG2E);
+#if AMP_DEN_EXACT_EXP
+    f2v f = {den_exp(lmx.x, smax.x), den_exp(lmx.y, smax.y)};
+#else
+    f2v targ = (lmx - smax) * l2e;
+    f2v f = {__builtin_amdgcn_exp2f(targ.x), __builtin_amdgcn_exp2f(targ.y)};
+#endif
+    f2v er[R], ei[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+#if AMP_DEN_EXACT_EXP
+        er[i] = f2v{den_exp(X[i].x, mx.x), den_exp(X[i].y, mx.y)};
+        ei[i] = f2v{den_exp(Y[i].x, my.x), den_exp(Y[i].y, my.y)};
+#else
+        const f2v xa = (X[i] - mx) * l2e, ya = (Y[i] - my) * l2e;
+        er[i] = f2v{__builtin_amdgcn_exp2f(xa.x), __builtin_amdgcn_exp2f(xa.y)};
+        ei[i] = f2v{__builtin_amdgcn_exp2f(ya.x), __builtin_amdgcn_exp2f(ya.y)};
+#endif
+    }
+    f2v zt, ar, ai, SI = f2splat(0.f);
+    f2v Sr[FULLG ? 1 : R];
+    if constexpr (FULLG) {
+        f2v sr = f2splat(0.f), si = f2splat(0.f), a = f2splat(0.f), b = f2splat(0.f);
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            sr += er[i]; si += ei[i];
+            a = f2fma(f2splat(Q.re[i]), er[i], a);
+            b = f2fma(f2splat(Q.im[i]), ei[i], b);
+        }
+        SI = si; Sr[0] = sr;
+        zt = (sr * si) * f;
+        ar = (a * si) * f;
+        ai = (sr * b) * f;
+    } else {
+        f2v z = f2splat(0.f), a = f2splat(0.f), b = f2splat(0.f), w[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) w[j] = f2splat(Q.im[j]) * ei[j];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            f2v si = f2splat(0.f), ti = f2splat(0.f);
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const float cw = grid_cnt<PAT>(i, j);
+                if (cw == 1.f) { si += ei[j]; ti += w[j]; }
+                else if (cw == 2.f) { si = f2fma(f2splat(2.f), ei[j], si); ti = f2fma(f2splat(2.f), w[j], ti); }
+            }
+            Sr[i] = si;
+            const f2v es = er[i] * si;
+            z += es;
+            a = f2fma(f2splat(Q.re[i]), es, a);
+            b = f2fma(er[i], ti, b);
+        }
+        zt = z * f;
+        ar = a * f;
+        ai = b * f;
+    }
+    float ze[2] = {0.f, 0.f}, zt1[2] = {zt.x, zt.y};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) group_sum_excl_c<G>(zt1[u], ze[u]);
+    const f2v iz = {den_rcp(zt1[0]), den_rcp(zt1[1])};
+    const f2v xr = ar * iz, xi = ai * iz;
+    f2v var = f2splat(0.f);
+    if (kVar) {
+        f2v vs;
+        if constexpr (FULLG) {
+            f2v vr = f2splat(0.f), vi = f2splat(0.f);
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                const f2v dr = xr - f2splat(Q.re[i]), di = xi - f2splat(Q.im[i]);
+                vr = f2fma(dr * dr, er[i], vr);
+                vi = f2fma(di * di, ei[i], vi);
+            }
+            vs = f2fma(vr, SI, Sr[0] * vi) * f;
+        } else {
+            f2v d[R];
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const f2v di = xi - f2splat(Q.im[j]);
+                d[j] = (di * di) * ei[j];
+            }
+            f2v acc = f2splat(0.f);
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                f2v vi = f2splat(0.f);
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    const float cw = grid_cnt<PAT>(i, j);
+                    if (cw == 1.f) vi += d[j];
+                    else if (cw == 2.f) vi = f2fma(f2splat(2.f), d[j], vi);
+                }
+                const f2v dr = xr - f2splat(Q.re[i]);
+                acc = f2fma(er[i], f2fma(dr * dr, Sr[i], vi), acc);
+            }
+            vs = acc * f;
+        }
+        const f2v zev = {ze[0], ze[1]};
+        var = (xr * xr + xi * xi) * (zev * iz) + vs * iz;
+    }
+    xr_out = xr; xi_out = xi; var_out = var; smax_out = smax; sabs_out = sabs;
+}
+
+// The packed step for a full round (both sections exist) with its inputs already loaded (rr, ri:
+// the two sections' r, vp: their previous variances; Grid2In): no masking and no control flow
+// between the loads and the stores.  The same operations on the same operands as
+// denoise_step_grid2, the accumulator updates in its order (u = 0, then u = 1); the section
+// statistics are stored by every lane of the group (the same value).  The policy supplies
+// load_r / load_prev / store_prev (the store with the previous variance handed in).
+struct Grid2In {
+    f2v rr, ri, vp;
+};
+template <int G, class P>
+__device__ __forceinline__ Grid2In grid2_load(const P& pol, int base) {
+    const int lane = threadIdx.x & 63;
+    constexpr int gpw = 64 / G;
+    const int gid = lane / G, g = lane % G;
+    Grid2In in;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        float rr, ri;
+        pol.load_r(base + u * gpw + gid, g, rr, ri);
+        in.rr[u] = rr; in.ri[u] = ri;
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) in.vp[u] = pol.load_prev(base + u * gpw + gid, g);
+    return in;
+}
+template <bool kVar, int R, int PAT, int G, class P>
+__device__ __forceinline__ void denoise_step_grid2_full(const P& pol, int base, const Grid2In& in, const GridRegs<R>& Q,
+                                                        PartAcc& pa, DenStat& S) {
+    const int lane = threadIdx.x & 63;
+    constexpr int gpw = 64 / G;
+    const int gid = lane / G, g = lane % G;
+    const f2v it = f2splat(pol.inv);
+    const f2v ur = in.rr * it, ui = in.ri * it;   // c64 / f32 == multiply by the reciprocal
+    const int bad = (int)!(fabsf(ur.x) <= FLT_MAX) | (int)!(fabsf(ui.x) <= FLT_MAX) | (int)!(fabsf(ur.y) <= FLT_MAX) |
+                    (int)!(fabsf(ui.y) <= FLT_MAX);
+    S.st_bad |= bad != 0;
+    f2v xr, xi, var, smax, sabs;
+    grid2_core<kVar, R, PAT, G>(ur, ui, Q, xr, xi, var, smax, sabs);
+    pol.store_xv(base + gid, g, xr.x, xi.x, var.x);
+    pol.store_xv(base + gpw + gid, g, xr.y, xi.y, var.y);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        pol.account(var[u], in.vp[u], pa);
+        S.st_abs = nan_max(S.st_abs, sabs[u]);
+        S.st_min = nan_min(S.st_min, smax[u]);
+        pol.section(base + u * gpw + gid, smax[u], sabs[u]);
+    }
+}
+
 #ifndef AMP_DEN_PACKED_GRID
 #define AMP_DEN_PACKED_GRID 1
 #endif
@@ -647,7 +825,12 @@ constexpr int grid_r() { return KK == 4 ? 2 : KK == 16 ? 4 : KK == 64 ? 8 : 0; }
 
 // The grid loop over this wave's sections; returns false (nothing done) when c is not a grid of
 // the size KK admits.  c.grid / c.gfull are kernel arguments: the branch is uniform.
-template <bool kVar, int KK, int U, int G, bool PKG = true, class P>
+// FAST (with the packed grid, U = 2; the policy supplies load_r / load_prev / store_xv / account):
+// this wave's full rounds (both sections of a step exist: base + 2 gpw <= nsec, wave-uniform) run
+// denoise_step_grid2_full; a partial last round runs the masked step.  The same bits either way.
+// (Requesting the next round's inputs before the current round's arithmetic was measured slower:
+// the six values held across the step spilled)
+template <bool kVar, int KK, int U, int G, bool PKG = true, bool FAST = false, class P>
 __device__ __forceinline__ bool denoise_sections_grid(const P& pol, int nsec, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block()) {
     constexpr int R = grid_r<KK>();
     if constexpr (R == 0) {
@@ -669,7 +852,13 @@ __device__ __forceinline__ bool denoise_sections_grid(const P& pol, int nsec, co
                     denoise_step_grid<kVar, R, GRID_FULL, U, G>(pol, base, nsec, Q, pa, S);
             }
         } else if constexpr (R == 4) {
-            for (int base = wave * gpw * U; base < nsec; base += nw * gpw * U) {
+            int base = wave * gpw * U;
+            if constexpr (FAST && PKG && U == 2 && AMP_DEN_PACKED_GRID) {
+                const int step = nw * gpw * 2;
+                for (; base + 2 * gpw <= nsec; base += step)
+                    denoise_step_grid2_full<kVar, R, GRID_REF16, G>(pol, base, grid2_load<G>(pol, base), Q, pa, S);
+            }
+            for (; base < nsec; base += nw * gpw * U) {
                 if constexpr (PKG && U == 2 && AMP_DEN_PACKED_GRID)
                     denoise_step_grid2<kVar, R, GRID_REF16, G>(pol, base, nsec, Q, pa, S);
                 else
@@ -707,25 +896,25 @@ __device__ __forceinline__ void denoise_sections_gp(const P& pol, int nsec, cons
 enum { PK_NONE = 0, PK_ALL = 1, PK_GRID = 2 };
 
 // Runtime M (a power of two <= 64) -> the compile-time group size.
-template <bool kVar, int KK, int U, int G, int PK, class P>
+template <bool kVar, int KK, int U, int G, int PK, bool FAST = false, class P>
 __device__ __forceinline__ void denoise_sections_sel(const P& pol, int nsec, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block()) {
     if constexpr (PK == PK_ALL && KK % 2 == 0) {
         denoise_sections_gp<kVar, KK, U, G>(pol, nsec, c, pa, dw);
     } else {
-        if (denoise_sections_grid<kVar, KK, U, G, PK == PK_GRID>(pol, nsec, c, pa, dw)) return;
+        if (denoise_sections_grid<kVar, KK, U, G, PK == PK_GRID, FAST>(pol, nsec, c, pa, dw)) return;
         denoise_sections_g<kVar, KK, U, G>(pol, nsec, c, pa, dw);
     }
 }
-template <bool kVar, int KK, int U, int PK = PK_ALL, class P>
+template <bool kVar, int KK, int U, int PK = PK_ALL, bool FAST = false, class P>
 __device__ __forceinline__ void denoise_sections_u(const P& pol, int nsec, int M, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block()) {
     switch (M) {
-    case 64: denoise_sections_sel<kVar, KK, U, 64, PK>(pol, nsec, c, pa, dw); break;
-    case 32: denoise_sections_sel<kVar, KK, U, 32, PK>(pol, nsec, c, pa, dw); break;
-    case 16: denoise_sections_sel<kVar, KK, U, 16, PK>(pol, nsec, c, pa, dw); break;
-    case 8: denoise_sections_sel<kVar, KK, U, 8, PK>(pol, nsec, c, pa, dw); break;
-    case 4: denoise_sections_sel<kVar, KK, U, 4, PK>(pol, nsec, c, pa, dw); break;
-    case 2: denoise_sections_sel<kVar, KK, U, 2, PK>(pol, nsec, c, pa, dw); break;
-    default: denoise_sections_sel<kVar, KK, U, 1, PK>(pol, nsec, c, pa, dw); break;
+    case 64: denoise_sections_sel<kVar, KK, U, 64, PK, FAST>(pol, nsec, c, pa, dw); break;
+    case 32: denoise_sections_sel<kVar, KK, U, 32, PK, FAST>(pol, nsec, c, pa, dw); break;
+    case 16: denoise_sections_sel<kVar, KK, U, 16, PK, FAST>(pol, nsec, c, pa, dw); break;
+    case 8: denoise_sections_sel<kVar, KK, U, 8, PK, FAST>(pol, nsec, c, pa, dw); break;
+    case 4: denoise_sections_sel<kVar, KK, U, 4, PK, FAST>(pol, nsec, c, pa, dw); break;
+    case 2: denoise_sections_sel<kVar, KK, U, 2, PK, FAST>(pol, nsec, c, pa, dw); break;
+    default: denoise_sections_sel<kVar, KK, U, 1, PK, FAST>(pol, nsec, c, pa, dw); break;
     }
 }
 

@@ -282,7 +282,28 @@ struct PDenoisePolicy {
         sm[sec] = smax;
         sa[sec] = sabs;
     }
-    float* dbg = nullptr;   // diagnostic: [16][2N] ze (columns < N) and vs (columns >= N), else null
+    // load and store in pieces (amp_denoise.h denoise_step_grid2_full: the loads of a step issued
+    // together, the stores together): load = load_r with it = inv; store = store_xv, then account
+    // with load_prev's value
+    __device__ __forceinline__ void load_r(int sec, int m, float& rr, float& ri) const {
+        const int row = sec >> lspr, sj = sec & ((1 << lspr) - 1);
+        const float2 v = *reinterpret_cast<const float2*>(r + row * ldr + 2 * (sj * M + m));
+        rr = v.x; ri = v.y;
+    }
+    __device__ __forceinline__ float load_prev(int sec, int m) const {
+        const int row = sec >> lspr, sj = sec & ((1 << lspr) - 1);
+        return vprev[row * N + sj * M + m];
+    }
+    __device__ __forceinline__ void store_xv(int sec, int m, float xr, float xi, float var) const {
+        const int row = sec >> lspr, sj = sec & ((1 << lspr) - 1);
+        *reinterpret_cast<float2*>(x + row * ldr + 2 * (sj * M + m)) = make_float2(xr, xi);
+        vnew[row * N + sj * M + m] = var;
+    }
+    __device__ __forceinline__ void account(float var, float vp, PartAcc& pa) const {
+        pa.sumvar += (double)var;
+        pa.notclose += torch_close(var, vp) ? 0u : 1u;     // vamp.py:185
+    }
+    float* dbg = nullptr;  // diagnostic: [16][2N] ze (columns < N) and vs (columns >= N), else null
 };
 __device__ __forceinline__ void den_debug(const PDenoisePolicy& p, int sec, int m, float ze, float vs) {
     if (p.dbg) {

@@ -30,6 +30,12 @@ constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iter
 #ifndef AMP_X3_W8_PKGRID
 #define AMP_X3_W8_PKGRID 1              // the eight-wave bf16x3 form keeps 16-QAM's packed grid denoiser
 #endif
+#ifndef AMP_X3_W8_DENFAST
+#define AMP_X3_W8_DENFAST 1             // the eight-wave form's full-round packed denoiser step (A/B builds: 0)
+#endif
+#ifndef AMP_DECIDE_NARROW
+#define AMP_DECIDE_NARROW 1             // the epilogue's narrowed candidate scan at one workgroup per CU (A/B builds: 0)
+#endif
 #ifndef AMP_X3_DU
 #define AMP_X3_DU 2                     // 16-QAM sections in flight per lane group (bf16x3 engine; 4 measured: no gain)
 #endif
@@ -103,6 +109,9 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // per-point form: the packed per-point form lost results there)
     constexpr int PKDEN = ((OCC * NWV / 4 == 1) || AMP_OCC2_PK) ? PK_ALL
                           : (NWV == 8 && KK == 16 && AMP_X3_W8_PKGRID) ? PK_GRID : PK_NONE;
+    // the eight-wave form at one workgroup per CU: the packed grid step's full rounds with no masking
+    // and no control flow between their loads and stores (amp_denoise.h denoise_sections_grid FAST)
+    constexpr bool DENFAST = NWV == 8 && OCC == 1 && PKDEN == PK_GRID && AMP_X3_W8_DENFAST;
     constexpr int PWG = 64 * NWV;
     constexpr int NC = X3 ? NT / 2 : 1;        // complex column tiles per wave (X3)
     constexpr int G3 = NT * NWV / 4;           // 32-wide complex reduction groups: N / 32
@@ -736,7 +745,7 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
         if constexpr (KK > 16)
             denoise_sections_wide_m<true, KK>(pol, nrows * spr, M, P.c, pa);
         else
-            denoise_sections_u<true, KK, DU, PKDEN>(pol, nrows * spr, M, P.c, pa);   // two waves per SIMD: scalar f32 (amp_denoise.h)
+            denoise_sections_u<true, KK, DU, PKDEN, DENFAST>(pol, nrows * spr, M, P.c, pa);   // two waves per SIMD: scalar f32 (amp_denoise.h)
         stamp(t, 8);
         const unsigned tag = P.gen * (unsigned)(P.max_iter + 1) + (unsigned)t + 1u;   // never 0 mod 2^32 in practice
         part_publish(pa, grs, ((unsigned)t * nwx + wgx) * 32u, tag, scr);
@@ -782,8 +791,9 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
         // the records are folded here, by the epoch's first workgroup of this launch, from the
         // tagged granules every workgroup publishes (no fold launch; tag unique per launch)
         const unsigned dtag = P.fold_in ? P.gen * (unsigned)(P.max_iter + 1) + (unsigned)P.max_iter + 1u : 0u;
-        decide_epilogue<PWG, KK, true>(P, dc, sR, sX, ldr, row0, lrow0, nrows, sA, lds + Y.offV0,
-                                       4 * (Y.offScr - Y.offV0), scr, dtag);
+        // one workgroup per CU: the narrowed candidate scan (amp_decide.h decide_section NARROW)
+        decide_epilogue<PWG, KK, true, OCC == 1 && AMP_DECIDE_NARROW>(P, dc, sR, sX, ldr, row0, lrow0, nrows, sA, lds + Y.offV0,
+                                                                      4 * (Y.offScr - Y.offV0), scr, dtag);
         const int nloc = nwg / P.E;                    // this launch's workgroups of one epoch
         if (P.fold_in && wg % nloc == 0) {             // wl == P.wg_off: the status writer above
             __syncthreads();

@@ -457,6 +457,15 @@ int amp_map_decide_count_rows(const amp_dims* d, const amp_constellation* c, con
                               int32_t ibits_trunc, int64_t row0, void* counts, void* decisions, void* ws,
                               size_t ws_bytes, void* stream);
 size_t amp_map_decide_workspace_bytes(const amp_dims* d);
+/* Diagnostic: the section decision of the persistent engines' fused epilogue (four lanes per
+ * section, rows staged in LDS, float32 prefilter before the float64 argmax) on caller-supplied
+ * rows; narrow != 0 runs the narrowed candidate scan vamp_persist uses, 0 the scan over every
+ * position.  N even and <= 256, M a power of two <= 64.  decisions: int32 [B*L] flat argmax
+ * m*K + k; mismatch: int32 [B*L] (xhat != x anywhere in the section, loss.py:133); sqerr:
+ * float64 [B*L] sum |xmmse - x|^2 over the section (loss.py:116). */
+int amp_decide_debug_sections(const amp_dims* d, const amp_constellation* c, const void* xmap,
+                              const void* xmmse, const void* x, int32_t narrow, void* decisions,
+                              void* mismatch, void* sqerr, void* stream);
 /* Same counters with Loss.random_decision (loss.py:252-280, generator_mode='random'): per
  * channel use the Na largest |x_m| (NaN largest; exact ties by larger index), each decided to
  * its nearest point, compared in ascending position order with the row's true sorted indices.

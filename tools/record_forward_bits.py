@@ -2,7 +2,11 @@
 """Records the bits of a building and of a reuse VAMP forward, with their inputs, as the fixture of
 tests/test_gpu_vamp_ring_prefill.py (tests/golden/ring_prefill_bits.part<k>.npz).
 
-  python tools/record_forward_bits.py [--out DIR]
+  python tools/record_forward_bits.py [--out DIR] [--stem STEM] [--cases "Nt,Na,Nr,B,alphabet;..."] [--share-channel]
+
+--stem / --cases record another fixture (tests/golden/<stem>.part<k>.npz) for another case list;
+--share-channel draws one channel, the first case's, stores it once ('shared/U', 's', 'Vh', 'SNR')
+and runs every case on it (the cases must agree in Nt and Nr).
 
 Public API only (Config, Channel, Data, VAMP, amp_native.prepare_counts), so the same script runs
 on any commit: a change that must leave the engine's results bit-identical is checked against a
@@ -41,22 +45,26 @@ def config(Nt, Na, Nr, B, alphabet, device):
                   channel_profile='uniform', channel_truncation='tail', device=device)
 
 
-def make_inputs(case):
-    """One channel and two epochs of messages + noise (host tensors), in the reference's call order."""
+def make_inputs(case, shared=None):
+    """One channel and two epochs of messages + noise (host tensors), in the reference's call order.
+    shared: the make_inputs result of another case whose channel (A, U, s, Vh, SNR) this one uses."""
     from channel import Channel
     from data import Data
     np.random.seed(SEED)
     torch.manual_seed(SEED)
     c = config(*case, device='cpu')
     ch, da = Channel(c), Data(c)
-    _, A = ch.generate_as_sparc()
-    U, s, Vh = torch.linalg.svd(A, full_matrices=False)
-    SNR = c.snr(EBN0[case[4]])
+    if shared is None:
+        _, A = ch.generate_as_sparc()
+        U, s, Vh = torch.linalg.svd(A, full_matrices=False)
+        SNR = c.snr(EBN0[case[4]])
+    else:
+        A, U, s, Vh, SNR = (shared[k] for k in ('A', 'U', 's', 'Vh', 'SNR'))
     eps = []
     for _ in range(2):
         x, sym, idx = da.generate_message()
         eps.append(dict(x=x, sym=sym, idx=idx, y=A @ x + ch.awgn(SNR)))
-    return dict(U=U, s=s, Vh=Vh, SNR=SNR, eps=eps)
+    return dict(A=A, U=U, s=s, Vh=Vh, SNR=SNR, eps=eps)
 
 
 def forward(det, chan, SNR, ep, device):
@@ -101,7 +109,7 @@ def packed(arrays):
     return buf.getvalue()
 
 
-def save(out, flat):
+def save(out, flat, stem=STEM):
     parts, cur = [], {}
     for name, a in flat.items():
         for k, b in chunked(name, a).items():
@@ -114,33 +122,44 @@ def save(out, flat):
     for k, arrays in enumerate(parts):
         raw = packed(arrays)
         assert len(raw) <= PART_LIMIT, (k, len(raw))
-        with open(os.path.join(out, f'{STEM}.part{k}.npz'), 'wb') as f:
+        with open(os.path.join(out, f'{stem}.part{k}.npz'), 'wb') as f:
             f.write(raw)
-        print(f'{STEM}.part{k}.npz: {len(raw)} bytes, {len(arrays)} arrays')
+        print(f'{stem}.part{k}.npz: {len(raw)} bytes, {len(arrays)} arrays')
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(REPO, 'tests', 'golden'))
+    ap.add_argument('--stem', default=STEM)
+    ap.add_argument('--cases', default=None, help='"Nt,Na,Nr,B,alphabet;..." (default: CASES)')
+    ap.add_argument('--share-channel', action='store_true',
+                    help="one channel, the first case's, stored once and used by every case")
     args = ap.parse_args()
+    cases = CASES if args.cases is None else [
+        tuple(int(v) for v in c.split(',')[:4]) + (c.split(',')[4],) for c in args.cases.split(';')]
     device = torch.device('cuda', 0)
     flat = {}
-    for case in CASES:
+    shared = None
+    for case in cases:
         name = case_name(*case)
-        inp = make_inputs(case)
+        inp = make_inputs(case, shared)
         res = run_case(case, inp, device)
         print(name, 'prepares (building, reuse) per forward:', [m for m, _ in res],
               'T:', [int(o['T'][0]) for _, o in res])
-        for k in ('U', 's', 'Vh'):
-            flat[f'{name}/{k}'] = as_np(inp[k])
-        flat[f'{name}/SNR'] = np.array([inp['SNR']], dtype=np.float64)
+        if args.share_channel and shared is None:
+            shared = inp
+        chan = 'shared' if args.share_channel else name
+        if f'{chan}/U' not in flat:
+            for k in ('U', 's', 'Vh'):
+                flat[f'{chan}/{k}'] = as_np(inp[k])
+            flat[f'{chan}/SNR'] = np.array([inp['SNR']], dtype=np.float64)
         for i, (ep, (made, o)) in enumerate(zip(inp['eps'], res)):
             for k in ('x', 'sym', 'idx', 'y'):
                 flat[f'{name}/f{i}_{k}'] = as_np(ep[k])
             flat[f'{name}/f{i}_made'] = np.array(made, dtype=np.int64)
             for k, v in o.items():
                 flat[f'{name}/f{i}_{k}'] = v
-    save(args.out, flat)
+    save(args.out, flat, args.stem)
 
 
 if __name__ == '__main__':

@@ -13,7 +13,7 @@
 
 using namespace amp;
 
-template <int KK, int U, int NWV, bool PK>
+template <int KK, int U, int NWV, int PK, bool FAST = false>
 __global__ __launch_bounds__(64 * NWV, 1) void ub(const float* rin, Const c, int N, int M, float inv, int reps,
                                                 unsigned long long* out, double* sink) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void ub(const float* rin, Const c, int
     unsigned long long t0 = __builtin_amdgcn_s_memtime();
     for (int r = 0; r < reps; ++r) {
         PDenoisePolicy pol{sR, sX, (r & 1) ? v1 : v0, (r & 1) ? v0 : v1, sm, sa, ldr, M, 31 - __builtin_clz(spr), N, inv};
-        denoise_sections_u<true, KK, U, PK>(pol, 16 * spr, M, c, pa);
+        denoise_sections_u<true, KK, U, PK, FAST>(pol, 16 * spr, M, c, pa);
         __syncthreads();
     }
     unsigned long long t1 = __builtin_amdgcn_s_memtime();
@@ -43,17 +43,17 @@ __global__ __launch_bounds__(64 * NWV, 1) void ub(const float* rin, Const c, int
     if ((threadIdx.x & 63) == 0) sink[blockIdx.x * NWV + (threadIdx.x >> 6)] = pa.sumvar + pa.notclose;
 }
 
-template <int KK, int U, int NWV, bool PK>
+template <int KK, int U, int NWV, int PK, bool FAST = false>
 static void run(const char* tag, const float* dr, const Const& c, int N, int M, float inv, unsigned long long* dout,
                 double* dsink) {
     const int nwg = 256, reps = 20;
     const size_t lds = (size_t)(2 * 16 * (2 * N + 4) + 2 * 16 * N + 2 * 16 * (N / M)) * 4;
-    hipFuncSetAttribute((const void*)ub<KK, U, NWV, PK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    for (int w = 0; w < 2; ++w) hipLaunchKernelGGL((ub<KK, U, NWV, PK>), dim3(nwg), dim3(64 * NWV), lds, 0, dr, c, N, M, inv, reps, dout, dsink);
+    hipFuncSetAttribute((const void*)ub<KK, U, NWV, PK, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    for (int w = 0; w < 2; ++w) hipLaunchKernelGGL((ub<KK, U, NWV, PK, FAST>), dim3(nwg), dim3(64 * NWV), lds, 0, dr, c, N, M, inv, reps, dout, dsink);
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0);
-    hipLaunchKernelGGL((ub<KK, U, NWV, PK>), dim3(nwg), dim3(64 * NWV), lds, 0, dr, c, N, M, inv, reps, dout, dsink);
+    hipLaunchKernelGGL((ub<KK, U, NWV, PK, FAST>), dim3(nwg), dim3(64 * NWV), lds, 0, dr, c, N, M, inv, reps, dout, dsink);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms;
@@ -61,7 +61,7 @@ static void run(const char* tag, const float* dr, const Const& c, int N, int M, 
     std::vector<unsigned long long> h(nwg);
     hipMemcpy(h.data(), dout, nwg * 8, hipMemcpyDeviceToHost);
     std::sort(h.begin(), h.end());
-    printf("%-28s K=%2d U=%d waves=%d pk=%d  median %7llu cyc/call  p90 %7llu  (kernel %.3f ms / %d reps)\n", tag, KK, U, NWV, (int)PK,
+    printf("%-28s K=%2d U=%d waves=%d pk=%d fast=%d  median %7llu cyc/call  p90 %7llu  (kernel %.3f ms / %d reps)\n", tag, KK, U, NWV, (int)PK, (int)FAST,
            h[nwg / 2], h[nwg * 9 / 10], ms, reps);
 }
 
@@ -105,6 +105,9 @@ extern "C" int ubench_main() {
     run<16, 2, 8, true>("cfg4 16QAM grid", dr, c, N, M, inv, dout, dsink);
     run<16, 2, 8, false>("cfg4 16QAM grid", dr, c, N, M, inv, dout, dsink);
     run<16, 1, 16, false>("cfg4 16QAM grid", dr, c, N, M, inv, dout, dsink);
+    // vamp_persist's eight-wave form (PK_GRID): the masked packed step, then its full-round form
+    run<16, 2, 8, PK_GRID, false>("cfg4 16QAM packed grid", dr, c, N, M, inv, dout, dsink);
+    run<16, 2, 8, PK_GRID, true>("cfg4 16QAM packed grid", dr, c, N, M, inv, dout, dsink);
     fflush(stdout);
     return 0;
 }
