@@ -171,7 +171,9 @@ bool allreduce_hook_set();
 int call_allreduce_hook(double* buf, int count, int op, hipStream_t st);
 int hook_failure(const char* what);   // sets the error text, returns AMP_E_LAUNCH
 
-int check_dims(const amp_dims* d, const amp_constellation* c, bool tiled = true);
+// tail_tile: the caller's column tiles take a partial last tile (2N % bn != 0 with 2N > bn) and its
+// GEMM operands an odd n (SCAMP: scamp_sld)
+int check_dims(const amp_dims* d, const amp_constellation* c, bool tiled = true, bool tail_tile = false);
 int device_cu_count();   // compute units of the current device (cached)
 // amp_stream_create_cu_range's registry (amp_weights.hip): the CU range of a stream it made, and the
 // claim of a range by one grid of a shard generation on an exchange buffer (false: the range

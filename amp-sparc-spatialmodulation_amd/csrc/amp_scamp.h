@@ -40,7 +40,7 @@ struct ScampK {
     const float* WAH;      // [ncpB][kapB]  A^H (z/phi)
     const float* y;        // [B][2n]
     float* z;              // [B][2n]
-    float* s;              // [B][2n] z / phi_use
+    float* s;              // [B][scamp_sld(n)] z / phi_use
     float* phi;            // [2][B][Lout] ping-pong
     float* tau;            // [B][Lin] (per iteration)
     float* xmap;           // caller [B][2N]
@@ -111,9 +111,12 @@ struct ScampWs {
 inline bool scamp_lx3_shape(const amp_dims* d) { return d->N % 64 == 0 && d->n % 64 == 0; }
 
 // 128 columns whenever a section fits (2M <= 128): twice the workgroups of a whole-coupling-
-// block tile (cfg3: 256 instead of 128).  A tile that does not hold whole coupling blocks
-// (2 Nt > BN) leaves psi to scamp_psi.
+// block tile (cfg3: 256 instead of 128).
 inline int scamp_bn(const amp_dims* d) { return section_bn(d); }
+// psi is formed in the A^H tile's epilogue only where every tile holds whole coupling blocks (Nt
+// divides the tile's bn / 2 complex columns: a power of two up to it); scamp_psi / tscamp_psi form it
+// after the tiles otherwise (blocks wider than a tile, or whose boundaries fall inside tiles).
+inline int scamp_psi_split(int bn, int Nt) { return (bn / 2) % Nt != 0 ? 1 : 0; }
 inline int scamp_psi_nblk(const amp_dims* d) { return std::max(1, std::min(cdiv(d->B * d->Lin, AMP_WG / 64), 2048)); }
 
 inline void scamp_geometry(const amp_dims* d, ScampK& P) {
@@ -125,15 +128,35 @@ inline void scamp_geometry(const amp_dims* d, ScampK& P) {
     P.nblk = cdiv(d->B, GBM) * (P.ncpB / P.bn);
 }
 
+bool scamp_persist_shape(const amp_dims* d);
+bool scamp_persist_eligible(const amp_dims* d, int ncu);
+bool scamp_persist_x3_fits(const amp_dims* d);
+
+// The kernels index trials x columns, sections and coupling blocks with 32-bit products and the
+// GEMM grids put the column tiles on gridDim.y: shapes beyond either are refused, never wrapped.
+// (The packed operators' offsets, ncp * kap floats, are 64-bit throughout.)
+inline bool scamp_index_ok(const amp_dims* d, int rows) {
+    const long long cols = 2LL * std::max(d->N, d->n);
+    return cols <= 0x7fffffffLL / 2 && (long long)rows * cols <= 0x7fffffffLL && cols / 128 + 1 <= 65535;
+}
+
+// Row stride of s = z / phi, the A operand of the A^H GEMM: 2n floats rounded up to the tile's
+// float4 loads (n odd: two pad floats per row, zeroed once by the init kernels; the operator's
+// reduction rows beyond 2n are zero).  z and y keep the caller's stride 2n.
+__host__ __device__ inline int scamp_sld(int n) { return (2 * n + 3) & ~3; }
+
 inline ScampWs scamp_carve(const amp_dims* d, int max_iter, void* base) {
     ScampK P;
     scamp_geometry(d, P);
+    // the persistent engines' operators and exchange buffers only where a persistent engine can run
+    // (no device query: the byte count is a function of the shape alone)
+    const bool persist = scamp_persist_shape(d) || scamp_persist_x3_fits(d);
     Carve cv(base);
     ScampWs w;
     w.WA = cv.take<float>((size_t)P.ncpA * P.kapA);
     w.WAH = cv.take<float>((size_t)P.ncpB * P.kapB);
     w.z = cv.take<float>((size_t)d->B * 2 * d->n);
-    w.s = cv.take<float>((size_t)d->B * 2 * d->n);
+    w.s = cv.take<float>((size_t)d->B * scamp_sld(d->n));
     w.phi = cv.take<float>((size_t)2 * d->B * d->Lout);
     w.tau = cv.take<float>((size_t)d->B * d->Lin);
     w.psi1 = cv.take<float>((size_t)d->B * d->Lin);
@@ -143,17 +166,17 @@ inline ScampWs scamp_carve(const amp_dims* d, int max_iter, void* base) {
     w.iters = cv.take<ScampIter>((size_t)max_iter + 1);
     w.psi_nc = cv.take<unsigned>((size_t)max_iter * scamp_psi_nblk(d));
     const int nwg = cdiv(d->B, 16);
-    w.Wq1 = cv.take<float>((size_t)2 * d->n * 2 * d->N);
-    w.Wq2 = cv.take<float>((size_t)2 * d->N * 2 * d->n);
-    w.Wx1 = cv.take<float>((size_t)3 * d->n * d->N);    // 6 bf16 per complex entry
-    w.Wx2 = cv.take<float>((size_t)3 * d->N * d->n);
-    w.pxch = cv.take<double>((size_t)max_iter * nwg * 4);
-    w.pbar = cv.take<unsigned>(64);
-    w.pparts = cv.take<Partial>((size_t)max_iter * nwg);
+    w.Wq1 = persist ? cv.take<float>((size_t)2 * d->n * 2 * d->N) : nullptr;
+    w.Wq2 = persist ? cv.take<float>((size_t)2 * d->N * 2 * d->n) : nullptr;
+    w.Wx1 = persist ? cv.take<float>((size_t)3 * d->n * d->N) : nullptr;    // 6 bf16 per complex entry
+    w.Wx2 = persist ? cv.take<float>((size_t)3 * d->N * d->n) : nullptr;
+    w.pxch = persist ? cv.take<double>((size_t)max_iter * nwg * 4) : nullptr;
+    w.pbar = cv.take<unsigned>(64);            // [8 ..]: the launch engine's arrival counters
+    w.pparts = persist ? cv.take<Partial>((size_t)max_iter * nwg) : nullptr;
     w.bandA = cv.take<int>((size_t)2 * (P.ncpA / 128));
     w.bandB = cv.take<int>((size_t)2 * (P.ncpB / P.bn));
     w.xs = cv.take<XState>(1);
-    w.dwg = cv.take<DecWG>((size_t)2 * nwg);   // 256 B of granules per workgroup
+    w.dwg = persist ? cv.take<DecWG>((size_t)2 * nwg) : nullptr;   // 256 B of granules per workgroup
     w.lap = scamp_lx3_shape(d) ? cv.take<unsigned short>((size_t)6 * round_up(d->B, GBM) * std::max(d->N, d->n))
                                : nullptr;
     w.bytes = cv.off;
@@ -170,8 +193,32 @@ __device__ __forceinline__ float scamp_gamma(const ScampK& P, const float* psi_r
     return g / (float)P.Lin;
 }
 
-bool scamp_persist_eligible(const amp_dims* d, int ncu);
-bool scamp_persist_x3_fits(const amp_dims* d);
+// sum |xmmse|^2 over one coupling block (scamp.py:59; torch abs = the correctly rounded hypot, then
+// an f32 square) by one wavefront: lane-strided float64 partials, then group_sum; every lane
+// returns the sum.  scamp_psi, tscamp_psi and the wide-block form of the float64 fix-up (Nt >
+// SFIX_SERIAL_NT) all go through it, so there a block's psi has the same bits whichever kernel
+// formed it.
+__device__ __forceinline__ double scamp_block_energy(const float2* xr, int Nt) {
+    double ssum = 0.0;
+    for (int m = threadIdx.x & 63; m < Nt; m += 64) {
+        const float2 v = xr[m];
+        const float a = (float)sqrt((double)v.x * v.x + (double)v.y * v.y);   // torch abs (hypot)
+        ssum += (double)(a * a);
+    }
+    return group_sum(ssum, 64);
+}
+
+// The fix-up kernels recompute a coupling block's psi with one thread per block up to this Nt (a
+// serial float64 sum over the block), with one wavefront per block (scamp_block_energy) beyond it.
+constexpr int SFIX_SERIAL_NT = 128;
+
+// Whether one of the block's `spb` sections was recomputed by the float64 fix-up (wavefront-uniform)
+__device__ __forceinline__ bool scamp_block_hit_wave(const float* secmax, int spb, double G, double slack) {
+    bool hit = false;
+    for (int j = threadIdx.x & 63; j < spb; j += 64) hit |= (double)secmax[j] - G < AMP_DANGER + slack;
+    return __any(hit) != 0;
+}
+
 int scamp_persist_launch(const ScampK& P, const DecConst& dc, hipStream_t st);
 
 }  // namespace amp

@@ -27,7 +27,7 @@ __global__ __launch_bounds__(AMP_WG) void scamp_ka(ScampK P, int t) {
     if (P.iters[t].stopped) return;
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
-    const int twoN = 2 * P.N, twon = 2 * P.n;
+    const int twoN = 2 * P.N, twon = 2 * P.n, sld = scamp_sld(P.n);
     const int kb = P.bandA ? P.bandA[2 * tile.cb] : 0, ke = P.bandA ? P.bandA[2 * tile.cb + 1] : -1;
     if constexpr (X3)
         gemm_tile_x3<128, true>(P.lap, P.rows_pad, P.N, P.WA, row0, col0, lds, kb, ke);
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(AMP_WG) void scamp_ka(ScampK P, int t) {
             const float ph = P.sigma2 + gma;
             const float iph = 1.0f / ph;
             *reinterpret_cast<float2*>(P.z + oc) = make_float2(zr, zi);
-            *reinterpret_cast<float2*>(P.s + oc) = make_float2(zr * iph, zi * iph);
+            *reinterpret_cast<float2*>(P.s + (size_t)row * sld + 2 * i) = make_float2(zr * iph, zi * iph);
             if (i % P.Nr == 0) phi_new[(size_t)row * P.Lout + lo] = ph;
         }
     }
@@ -138,12 +138,12 @@ __global__ __launch_bounds__(AMP_WG) void scamp_kb(ScampK P, int t) {
     using C = GemmCfg<BN, KC>;
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    const int twoN = 2 * P.N, twon = 2 * P.n;
+    const int twoN = 2 * P.N, sld = scamp_sld(P.n);
     const int kb = P.bandB ? P.bandB[2 * tile.cb] : 0, ke = P.bandB ? P.bandB[2 * tile.cb + 1] : -1;
     if constexpr (X3)
         gemm_tile_x3<BN, true>(P.lap, P.rows_pad, P.n, P.WAH, row0, col0, lds, kb, ke);
     else
-        gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, twon, P.B, twon}, P.WAH, P.kapB, row0, col0, lds, kb, ke);
+        gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, sld, P.B, sld}, P.WAH, P.kapB, row0, col0, lds, kb, ke);
     const int nrows = min(GBM, P.B - row0), ncols = min(BN, twoN - col0);
     const int lc0 = (col0 / 2) / P.Nt, nlc = max(1, (ncols / 2) / P.Nt);   // coupling blocks in this tile
     // tau of the blocks this tile covers only (blocks lc0 .. lc0 + ntc - 1): each is written to
@@ -258,14 +258,7 @@ __global__ __launch_bounds__(AMP_WG) void scamp_psi(ScampK P, int t) {
     const int nwave = gridDim.x * (AMP_WG / 64);
     unsigned nc = 0;
     for (int blk = blockIdx.x * (AMP_WG / 64) + (threadIdx.x >> 6); blk < P.B * P.Lin; blk += nwave) {
-        const float2* xr = reinterpret_cast<const float2*>(P.xm) + (size_t)blk * P.Nt;
-        double ssum = 0.0;
-        for (int m = lane; m < P.Nt; m += 64) {
-            const float2 v = xr[m];
-            const float a = (float)sqrt((double)v.x * v.x + (double)v.y * v.y);   // torch abs (hypot)
-            ssum += (double)(a * a);
-        }
-        ssum = group_sum(ssum, 64);
+        const double ssum = scamp_block_energy(reinterpret_cast<const float2*>(P.xm) + (size_t)blk * P.Nt, P.Nt);
         if (lane == 0) {
             const float ps = 1.0f - (float)ssum / (float)P.Na;
             nc += torch_close(ps, psi_prev[blk]) ? 0u : 1u;
@@ -404,6 +397,20 @@ __device__ __forceinline__ void scamp_fix_psi_body(const ScampK& P, int t, const
     float* psi_new = spsi(P, t);
     const int spb = P.Nt / P.M;   // sections per coupling block
     int dnc = 0;
+    if (P.Nt > SFIX_SERIAL_NT) {
+        // wide blocks: one wavefront per block, in scamp_psi's summation order
+        const int nwave = gridDim.x * (blockDim.x >> 6);
+        for (int blk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); blk < P.B * P.Lin; blk += nwave) {
+            if (!scamp_block_hit_wave(P.secmax + (size_t)blk * spb, spb, pend.G, pend.slack)) continue;
+            const float2* xr = reinterpret_cast<const float2*>(P.xm) + (size_t)blk * P.Nt;
+            const double ssum = scamp_block_energy(xr, P.Nt);
+            if ((threadIdx.x & 63) == 0) {
+                const float ps = 1.0f - (float)ssum / (float)P.Na;
+                dnc += (torch_close(ps, psi_prev[blk]) ? 0 : 1) - (torch_close(psi_new[blk], psi_prev[blk]) ? 0 : 1);
+                psi_new[blk] = ps;
+            }
+        }
+    } else
     for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < P.B * P.Lin; blk += gridDim.x * blockDim.x) {
         bool hit = false;
         for (int j = 0; j < spb && !hit; ++j)
@@ -566,6 +573,8 @@ __global__ void scamp_init_kernel(ScampK P) {
         if (e < Bn) reinterpret_cast<float2*>(P.z)[e] = reinterpret_cast<const float2*>(P.y)[e];
         if (e < (size_t)P.B * P.Lin) P.psi1[e] = 1.0f;
         if (e < BL) P.phi[BL + e] = INFINITY;        // phi buffer of "iteration -1"
+        if (e < (size_t)P.B)                         // the pad of an odd n's s rows (scamp_sld)
+            for (int k = 2 * P.n; k < scamp_sld(P.n); ++k) P.s[e * scamp_sld(P.n) + k] = 0.f;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         P.rcnt[0] = 0u; P.rcnt[1] = 0u;
@@ -715,13 +724,16 @@ static bool band_gemm_enabled() {
 
 static int scamp_setup(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a, ScampK& P,
                        Const64& c64) {
-    int rc = check_dims(d, c);
+    // any Nt whose section size M = Nt / Na is a power of two (check_dims); the A^H column tiles
+    // take coupling blocks of any width and a partial last tile
+    int rc = check_dims(d, c, true, true);
     if (rc) return rc;
     AMP_REQUIRE(a && a->W && a->A && a->y && a->xmap && a->xmmse && a->psi && a->status && a->ws,
                 "amp_scamp_run: null pointer argument");
     AMP_REQUIRE(a->max_iter > 0, "amp_scamp_run: max_iter must be positive");
-    AMP_REQUIRE(is_pow2(d->Nt) && 2 * d->Nt <= 256, "amp_scamp_run: Nt = %d must be a power of two <= 128", d->Nt);
     AMP_REQUIRE(d->Lin <= SMAXLIN, "amp_scamp_run: Lin = %d > %d", d->Lin, SMAXLIN);
+    AMP_REQUIRE(scamp_index_ok(d, d->B), "amp_scamp_run: B = %d trials of max(2N, 2n) = %d columns need more than "
+                "32-bit offsets (or more than 65535 column tiles)", d->B, 2 * std::max(d->N, d->n));
     const ScampWs w = scamp_carve(d, a->max_iter, a->ws);
     AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_scamp_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
     rc = scamp_attrs();
@@ -740,7 +752,7 @@ static int scamp_setup(const amp_dims* d, const amp_constellation* c, const amp_
     P.y = (const float*)a->y; P.z = w.z; P.s = w.s; P.phi = w.phi; P.tau = w.tau;
     P.xmap = (float*)a->xmap; P.xm = (float*)a->xmmse; P.psi0 = (float*)a->psi; P.psi1 = w.psi1;
     P.secmax = w.secmax; P.secabs = w.secabs; P.parts = w.parts; P.iters = w.iters; P.status = (amp_status*)a->status;
-    P.psi_nc = w.psi_nc; P.psi_nblk = scamp_psi_nblk(d); P.psi_split = (P.bn / 2 < P.Nt) ? 1 : 0;
+    P.psi_nc = w.psi_nc; P.psi_nblk = scamp_psi_nblk(d); P.psi_split = scamp_psi_split(P.bn, P.Nt);
     P.nwg = cdiv(d->B, 16);
     P.gen = 0;
     P.Wq1 = w.Wq1; P.Wq2 = w.Wq2; P.pparts = w.pparts; P.pxch = w.pxch; P.pbar = w.pbar;

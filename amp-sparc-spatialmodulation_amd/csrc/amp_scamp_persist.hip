@@ -28,15 +28,20 @@
 namespace amp {
 
 bool scamp_persist_x3_fits(const amp_dims* d) {
+    if (std::max(d->N, d->n) > 160 * 1024) return false;   // far beyond the LDS (and the layout's int sums)
     return (size_t)slayout(d->N, d->n, d->L, d->Lin, d->Lout, true).total * 4 + 1024 <= 160 * 1024;
 }
 
-bool scamp_persist_eligible(const amp_dims* d, int ncu) {
+// the part of the eligibility that depends on the shape alone (scamp_carve: no device query)
+bool scamp_persist_shape(const amp_dims* d) {
     const int twoN = 2 * d->N, twon = 2 * d->n;
     const bool shape = (twoN == 128 && twon == 256) || (twoN == 256 && twon == 512) || (twoN == 256 && twon == 256);
     if (!shape || d->M > 64 || d->Lin > SMAXLIN || d->Lout > SMAXLIN || !is_pow2(d->N / d->M)) return false;
-    if (ncu <= 0 || cdiv(d->B, SPB) > ncu) return false;
     return (size_t)slayout(d->N, d->n, d->L, d->Lin, d->Lout).total * 4 + 1024 <= 160 * 1024;
+}
+
+bool scamp_persist_eligible(const amp_dims* d, int ncu) {
+    return scamp_persist_shape(d) && ncu > 0 && cdiv(d->B, SPB) <= ncu;
 }
 
 // NT1 = 2n / 64 column tiles per wave (GEMM1, K = 2N = 16 G1); NT2 = 2N / 64 (GEMM2, K = 2n)

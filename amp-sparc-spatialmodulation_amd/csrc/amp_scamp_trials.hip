@@ -43,7 +43,7 @@ struct TScampK {
     const float* WAH;      // [ncpB][kapB]  A^H (z/phi)
     const float* y;        // [E][2n]
     float* z;              // [E][2n]
-    float* s;              // [E][2n] z / phi_use
+    float* s;              // [E][scamp_sld(n)] z / phi_use
     float* phi;            // [2][E][Lout] ping-pong
     float* tau;            // [E][Lin] (per iteration)
     float* xmap;           // caller [E][2N]
@@ -82,7 +82,7 @@ static void tscamp_geometry(const amp_dims* d, int E, TScampK& P) {
     P.kapA = round_up(2 * d->N, GBK); P.ncpA = round_up(2 * d->n, 128);
     P.kapB = round_up(2 * d->n, GBK); P.ncpB = round_up(2 * d->N, P.bn);
     P.nct = P.ncpB / P.bn;
-    P.psi_split = (P.bn / 2 < P.Nt) ? 1 : 0;
+    P.psi_split = scamp_psi_split(P.bn, P.Nt);
 }
 
 static TScampWs tscamp_carve(const amp_dims* d, int E, void* base) {
@@ -93,7 +93,7 @@ static TScampWs tscamp_carve(const amp_dims* d, int E, void* base) {
     w.WA = cv.take<float>((size_t)P.ncpA * P.kapA);
     w.WAH = cv.take<float>((size_t)P.ncpB * P.kapB);
     w.z = cv.take<float>((size_t)E * 2 * d->n);
-    w.s = cv.take<float>((size_t)E * 2 * d->n);
+    w.s = cv.take<float>((size_t)E * scamp_sld(d->n));
     w.phi = cv.take<float>((size_t)2 * E * d->Lout);
     w.tau = cv.take<float>((size_t)E * d->Lin);
     w.psi1 = cv.take<float>((size_t)E * d->Lin);
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(AMP_WG) void tscamp_ka(TScampK P, int t) {
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
     if (!tile_rows_live(P.iters, row0, P.E, s_stop)) return;
-    const int twoN = 2 * P.N, twon = 2 * P.n;
+    const int twoN = 2 * P.N, twon = 2 * P.n, sld = scamp_sld(P.n);
     const int kb = P.bandA ? P.bandA[2 * tile.cb] : 0, ke = P.bandA ? P.bandA[2 * tile.cb + 1] : -1;
     gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.xm, twoN, P.E, twoN}, P.WA, P.kapA, row0, col0, lds, kb, ke);
     using C = GemmCfg<128, 256>;
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(AMP_WG) void tscamp_ka(TScampK P, int t) {
             const float ph = P.sigma2 + gma;
             const float iph = 1.0f / ph;
             *reinterpret_cast<float2*>(P.z + oc) = make_float2(zr, zi);
-            *reinterpret_cast<float2*>(P.s + oc) = make_float2(zr * iph, zi * iph);
+            *reinterpret_cast<float2*>(P.s + (size_t)row * sld + 2 * i) = make_float2(zr * iph, zi * iph);
             if (i % P.Nr == 0) phi_new[(size_t)row * P.Lout + lo] = ph;
         }
     }
@@ -233,9 +233,9 @@ __global__ __launch_bounds__(AMP_WG) void tscamp_kb(TScampK P, int t) {
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
     if (!tile_rows_live(P.iters, row0, P.E, s_stop)) return;
-    const int twoN = 2 * P.N, twon = 2 * P.n;
+    const int twoN = 2 * P.N, sld = scamp_sld(P.n);
     const int kb = P.bandB ? P.bandB[2 * tile.cb] : 0, ke = P.bandB ? P.bandB[2 * tile.cb + 1] : -1;
-    gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, twon, P.E, twon}, P.WAH, P.kapB, row0, col0, lds, kb, ke);
+    gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, sld, P.E, sld}, P.WAH, P.kapB, row0, col0, lds, kb, ke);
     const int nrows = min(GBM, P.E - row0), ncols = min(BN, twoN - col0);
     const int lc0 = (col0 / 2) / P.Nt, nlc = max(1, (ncols / 2) / P.Nt);   // coupling blocks in this tile
     // tau of the blocks this tile covers only (blocks lc0 .. lc0 + ntc - 1): each is written to
@@ -341,14 +341,7 @@ __global__ __launch_bounds__(AMP_WG) void tscamp_psi(TScampK P, int t) {
     const int nwave = gridDim.x * (AMP_WG / 64);
     for (int blk = blockIdx.x * (AMP_WG / 64) + (threadIdx.x >> 6); blk < P.E * P.Lin; blk += nwave) {
         if (P.iters[blk / P.Lin].stopped) continue;   // wavefront-uniform
-        const float2* xr = reinterpret_cast<const float2*>(P.xm) + (size_t)blk * P.Nt;
-        double ssum = 0.0;
-        for (int m = lane; m < P.Nt; m += 64) {
-            const float2 v = xr[m];
-            const float a = (float)sqrt((double)v.x * v.x + (double)v.y * v.y);   // torch abs (hypot)
-            ssum += (double)(a * a);
-        }
-        ssum = group_sum(ssum, 64);
+        const double ssum = scamp_block_energy(reinterpret_cast<const float2*>(P.xm) + (size_t)blk * P.Nt, P.Nt);
         if (lane == 0) {
             const float ps = 1.0f - (float)ssum / (float)P.Na;
             P.psi_nc[blk] = torch_close(ps, psi_prev[blk]) ? 0u : 1u;
@@ -492,6 +485,19 @@ __global__ __launch_bounds__(TSRWG) void tscamp_fix_psi_fin(TScampK P, int t) {
     const float* secmax = P.secmax + (size_t)e * P.L;
     const int spb = P.Nt / P.M;   // sections per coupling block
     int dnc = 0;
+    if (P.Nt > SFIX_SERIAL_NT) {
+        // wide blocks: one wavefront per block, in tscamp_psi's summation order (scamp_fix_psi_body)
+        for (int blk = threadIdx.x >> 6; blk < P.Lin; blk += blockDim.x >> 6) {
+            if (!scamp_block_hit_wave(secmax + (size_t)blk * spb, spb, pend.G, pend.slack)) continue;
+            const double ssum = scamp_block_energy(
+                reinterpret_cast<const float2*>(P.xm) + (size_t)e * P.N + (size_t)blk * P.Nt, P.Nt);
+            if ((threadIdx.x & 63) == 0) {
+                const float ps = 1.0f - (float)ssum / (float)P.Na;
+                dnc += (torch_close(ps, psi_prev[blk]) ? 0 : 1) - (torch_close(psi_new[blk], psi_prev[blk]) ? 0 : 1);
+                psi_new[blk] = ps;
+            }
+        }
+    } else
     for (int blk = threadIdx.x; blk < P.Lin; blk += blockDim.x) {
         bool hit = false;
         for (int j = 0; j < spb && !hit; ++j)
@@ -520,6 +526,8 @@ __global__ void tscamp_init_kernel(TScampK P) {
         if (e < En) reinterpret_cast<float2*>(P.z)[e] = reinterpret_cast<const float2*>(P.y)[e];
         if (e < (size_t)P.E * P.Lin) P.psi1[e] = 1.0f;
         if (e < EL) P.phi[EL + e] = INFINITY;        // phi buffer of "iteration -1"
+        if (e < (size_t)P.E)                         // the pad of an odd n's s rows (scamp_sld)
+            for (int k = 2 * P.n; k < scamp_sld(P.n); ++k) P.s[e * scamp_sld(P.n) + k] = 0.f;
         if (e < (size_t)P.E) {
             TScampIter it;
             it.stopped = 0; it.T = 0; it.fixed = 0; it.fixed_all = 0;
@@ -578,7 +586,11 @@ static void tscamp_launch_kb(const TScampK& P, int gr, int t, hipStream_t st) {
     }
 }
 
-static bool tscamp_shape_ok(const amp_dims* d) { return is_pow2(d->Nt) && 2 * d->Nt <= 256 && d->Lin <= SMAXLIN; }
+// any Nt (amp_scamp_run's shapes); the byte query answers 0 for dims the run would refuse
+static bool tscamp_shape_ok(const amp_dims* d, int E) {
+    return d->Nt > 0 && d->Na > 0 && d->Nr > 0 && d->Lin > 0 && d->Lout > 0 && d->Lin <= SMAXLIN &&
+           d->N == d->Nt * d->Lin && d->n == d->Nr * d->Lout && scamp_index_ok(d, E);
+}
 
 }  // namespace amp
 
@@ -587,22 +599,22 @@ using namespace amp;
 extern "C" {
 
 size_t amp_scamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials) {
-    if (!d || max_iter <= 0 || trials <= 0 || d->B != 1 || !tscamp_shape_ok(d)) return 0;
+    if (!d || max_iter <= 0 || trials <= 0 || d->B != 1 || !tscamp_shape_ok(d, trials)) return 0;
     return tscamp_carve(d, trials, nullptr).bytes;
 }
 
 int amp_scamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
                          const amp_trials_decide_args* dec, int32_t trials, void* stream) {
-    int rc = check_dims(d, c);
+    int rc = check_dims(d, c, true, true);   // any Nt, a partial last column tile (amp_scamp_run)
     if (rc) return rc;
     AMP_REQUIRE(d->B == 1, "amp_scamp_trials_run: dims describe ONE trial (B = %d, must be 1)", d->B);
     AMP_REQUIRE(trials >= 1, "amp_scamp_trials_run: trials = %d", trials);
     AMP_REQUIRE(a && a->W && a->A && a->y && a->xmap && a->xmmse && a->psi && a->status && a->ws,
                 "amp_scamp_trials_run: null pointer argument");
     AMP_REQUIRE(a->max_iter > 0, "amp_scamp_trials_run: max_iter must be positive");
-    AMP_REQUIRE(is_pow2(d->Nt) && 2 * d->Nt <= 256, "amp_scamp_trials_run: Nt = %d must be a power of two <= 128",
-                d->Nt);
     AMP_REQUIRE(d->Lin <= SMAXLIN, "amp_scamp_trials_run: Lin = %d > %d", d->Lin, SMAXLIN);
+    AMP_REQUIRE(scamp_index_ok(d, trials), "amp_scamp_trials_run: %d trials of max(2N, 2n) = %d columns need more "
+                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
     AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES,
                 "amp_scamp_trials_run: launch engine only (engine %d)", a->engine);
     AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "amp_scamp_trials_run: f32 GEMMs only (gemm %d)",
