@@ -262,14 +262,17 @@ __device__ __forceinline__ void x3_ring_fill(X3Ring<NT, x3_ring_depth(G, R)>& ri
 }
 
 // hook(g): called behind group g's MFMAs, before its ring slot is refilled (the microbenchmark's
-// start-up stamp, tools/ubench/ring_prefill_ubench.hip; the engines pass none).
+// start-up stamp, tools/ubench/ring_prefill_ubench.hip; the engines pass none).  after(g): called
+// behind the refill's requests, before the next group (vamp_persist's scalar tail).
 struct X3NoHook {
     __device__ __forceinline__ void operator()(int) const {}
 };
-template <int NT, int G, int R = 1, bool PIN = false, bool HL = false, bool NEXT = false, class Hook = X3NoHook>
+template <int NT, int G, int R = 1, bool PIN = false, bool HL = false, bool NEXT = false, class Hook = X3NoHook,
+          class After = X3NoHook>
 __device__ __forceinline__ void gemm_x3_ring(const unsigned short* sP, int ldx, const void* __restrict__ wq, int ct0,
                                              X3Ring<NT, x3_ring_depth(G, R)>& ring, f32x4 (&cr)[NT], f32x4 (&ci)[NT],
-                                             const void* __restrict__ wq_next = nullptr, Hook&& hook = Hook()) {
+                                             const void* __restrict__ wq_next = nullptr, Hook&& hook = Hook(),
+                                             After&& after = After()) {
     constexpr int RR = x3_ring_depth(G, R);
     static_assert(!NEXT || G % RR == 0, "the next operator's group j lands in slot j % RR");
     constexpr int NL = HL ? NT : 1;
@@ -345,6 +348,7 @@ __device__ __forceinline__ void gemm_x3_ring(const unsigned short* sP, int ldx, 
         } else if constexpr (NEXT) {
             x3_ring_load<NT, G>(ring, d, x3_wrsrc<G>(wq_next, ct0), g + RR - G);
         }
+        after(g);
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (HL) {

@@ -40,6 +40,8 @@ struct VampK {
     int nwg;            // workgroups: E * wpe
     int E, wpe;         // side-by-side epochs (independent batches of B trials, one channel) and
                         // workgroups per epoch (ceil(B / PBM)); E = 1 outside amp_vamp_detect_count_epochs
+    float etaf;         // (float)eta, eta = (double)k / (double)N (vamp.py:28, 73): a launch constant formed by
+                        // vamp_geometry (vamp_advance_tail); here and below in words that were padding
     const float* Wq1;   // Vh   16x16x4-packed [2k][2N]
     const float* Wq2;   // V    16x16x4-packed [2N][2k]
     Partial* pparts;    // [max_iter][nwg] 32-B granule pairs (amp_vamp_persist.hip), right after pbar
@@ -59,6 +61,7 @@ struct VampK {
                                 // persistent engine folds them itself, amp_decide_fused.h)
     unsigned char* host_rec;    // optional page-locked host record (amp_vamp_decide_args.host_record)
     int fold_in;                // the persistent kernel folds the records itself (else vamp_decide_fold)
+    float ometaf;               // (float)(1.0 - eta) (vamp.py:73; see etaf)
     amp_counts* counts;         // out
     unsigned long long* trace;   // diagnostic phase stamps (amp_vamp_persist_trace), else null
     int x3;                      // persistent engine GEMMs: 0 f32 MFMA, 1 bf16x3, 2 fp16x2 (Wx1 / Wx2)
@@ -104,6 +107,8 @@ struct VampWs {
 static void vamp_geometry(const amp_dims* d, int k, VampK& P) {
     P.Na = d->Na; P.Lin = d->Lin;
     P.B = d->B; P.N = d->N; P.n = d->n; P.k = k; P.L = d->L; P.M = d->M;
+    const double eta = (double)k / (double)d->N;   // vamp.py:28: the division and the roundings of vamp_lmmse_scalars
+    P.etaf = (float)eta; P.ometaf = (float)(1.0 - eta);
     P.kap0 = round_up(2 * d->n, GBK); P.ncp0 = round_up(2 * k, 128);
     P.kap1 = round_up(2 * d->N, GBK); P.ncp1 = round_up(2 * k, 128);
     P.bn2 = section_bn(d);
@@ -241,6 +246,59 @@ __device__ inline VampIter vamp_advance(const VampK& P, const VampIter& cur, con
         vamp_lmmse_scalars(P, false, 0.0, s2t, lds, nx, sl);
     }
     return nx;
+}
+
+// vamp_advance in two parts, for the persistent engine at one workgroup per CU: every operation
+// keeps its operands, its type and its order; only the time at which it is issued differs.
+// Head: the stop test and what the r~ build of iteration t+1 needs (dxdr, normScalar), with
+// sigma2_tilde left in nx.s2t.  On a stop the record is complete (a copy of cur); otherwise vr,
+// alpha, inv1ma, sigma2 and inv_sigma2 are vamp_advance_tail's.
+__device__ inline VampIter vamp_advance_head(const VampK& P, const VampIter& cur, const PartAcc& pa, int fixed, int t) {
+    VampIter nx;
+    nx.stopped = 0; nx.T = 0; nx.fixed = fixed; nx.fixed_all = (fixed < 0) ? 1 : 0; nx.G = pa.maxabs;
+    nx.pad1[0] = nx.pad1[1] = nx.pad1[2] = 0.f;
+    nx.vr = nx.alpha = nx.inv1ma = nx.sigma2 = nx.inv_sigma2 = 0.f;
+    if (pa.notclose == 0) {                                              // vamp.py:185-186
+        nx = cur;
+        nx.stopped = 1;
+        nx.T = t + 1;
+        nx.fixed = fixed;
+    } else {
+        const float mean = (float)(pa.sumvar / ((double)P.Bmean * (double)P.N));
+        const float dxdr = clampf_t(mean / cur.sigma2, AMP_VAR_RATIO_MIN, 1.0f - AMP_VAR_RATIO_MIN);  // vamp.py:85-87
+        const float ns = 1.0f / (1.0f - dxdr);                                                        // vamp.py:89
+        nx.dxdr_prev = dxdr;
+        nx.ns_prev = ns;
+        nx.s2t = clampf_t((cur.sigma2 * dxdr) * ns, AMP_VAR_MIN, AMP_VAR_MAX);                        // vamp.py:92-94
+    }
+    return nx;
+}
+
+// Tail: vamp_lmmse_scalars(first = false) from it.s2t and this lane's s^2.  The four reciprocals
+// are formed unconditionally (no exec-masked region, no wait of its own per term) and added in j
+// order with a select: an invalid term adds +0.0 to a sum that is never -0.0 (it starts at +0.0),
+// which leaves its bits (s2_lane holds 0 there: the discarded quotient is finite or inf).  eta's
+// two roundings come from the host (VampK.etaf / ometaf).
+__device__ inline void vamp_advance_tail(const VampK& P, VampIter& it, const S2Lane& sl) {
+    const float s2t = it.s2t;
+    const float vr = (1.0f / s2t) * (float)P.noise_var;                                        // vamp.py:66
+    const int lane = threadIdx.x & 63;
+    float q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = 1.0f / (sl.v[j] + vr);                                  // vamp.py:17, 68
+    double ss = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ss += (lane + 64 * j < P.k) ? (double)q[j] : 0.0;
+    ss = group_sum(ss, 64);
+    const float varL = (float)(ss / (double)P.k) * (float)P.noise_var;                         // vamp.py:71
+    const float xtv = P.etaf * varL + P.ometaf * s2t;                                          // vamp.py:73
+    const float alpha = clampf_t(xtv / s2t, AMP_VAR_RATIO_MIN, 1.0f - AMP_VAR_RATIO_MIN);      // vamp.py:75-77
+    const float sigma2 = clampf_t((alpha / (1.0f - alpha)) * s2t, AMP_VAR_MIN, AMP_VAR_MAX);   // vamp.py:80-82
+    it.vr = vr;
+    it.alpha = alpha;
+    it.inv1ma = 1.0f / (1.0f - alpha);
+    it.sigma2 = sigma2;
+    it.inv_sigma2 = 1.0f / sigma2;
 }
 
 __device__ inline amp_status vamp_make_status(const VampK& P, const VampIter& cur, const VampIter& nx, int fixed) {

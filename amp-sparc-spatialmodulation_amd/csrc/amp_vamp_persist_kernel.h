@@ -39,6 +39,9 @@ constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iter
 #ifndef AMP_X3_DU
 #define AMP_X3_DU 2                     // 16-QAM sections in flight per lane group (bf16x3 engine; 4 measured: no gain)
 #endif
+#ifndef AMP_SCALAR_TAIL
+#define AMP_SCALAR_TAIL 1               // bf16x3 at one workgroup per CU: the LMMSE scalars of vamp_advance inside the
+#endif                                  // next iteration's GEMM1, behind group 0 (A/B builds: 0, the unsplit form)
 
 // LDS carve (floats).  Row strides 2N+4 / max(2N,2k)+4 keep the f32 engine's 16-row ds_read_b128
 // and accumulator stores conflict-free (row r and r+4 land 16 banks apart); the split-precision
@@ -122,12 +125,18 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // bf16x3: each GEMM's operator ring is filled one phase ahead (x3_ring_fill / gemm_x3_ring)
     constexpr bool X3PF = X3 && !H2 && !I8;
     constexpr int PFT = (NC + 1) / 2;          // GEMM1's fill: tiles 0 .. PFT - 1 before the r~ plane build, the rest behind it
+    // vamp_advance in two parts (amp_vamp.h): the exchange forms only what the r~ build needs (the
+    // head), the LMMSE scalars of the record (the tail: vr for the w epilogue, alpha and inv1ma for
+    // r_epi, inv_sigma2 for the denoiser) follow inside the next iteration's GEMM1 (DESIGN.md §3.1:
+    // -3.6 to -10 us per cfg4 step, though the traced GEMM1 grows by the tail's length)
+    constexpr int STAIL = (X3PF && OCC == 1) ? AMP_SCALAR_TAIL : 0;
 #define c64 (static_cast<const Const64&>(*Dp))
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_flag;
     __shared__ double s_d[PWG / 64][4];
     __shared__ float s_hmax[PWG / 64][PBM];   // H2: per-wave row maxima of the A operand
     __shared__ int s_hexp[PBM];               // H2: r~ row exponents (for GEMM1's epilogue)
+    __shared__ float s_s2[STAIL != 0 ? 256 : 1];   // the split form: s^2 (k <= 256; 0 from k on) for the tail's LMMSE sum
     const PLayout Y = playout(P.N, P.k, P.L, X3);
     float* sA = lds + Y.offA;
     float* sR = lds + Y.offR;
@@ -280,6 +289,15 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     {
         const S2Lane s2l = s2_lane(P, sv_ep);     // s^2 for the first LMMSE sum (re-read per exchange below)
         cur = vamp_first_iter(P, scr, &s2l);      // vamp.py:26, 66-82 at t = 0
+        // the split form reads them from LDS in every later iteration (s2_lane's values; the first
+        // read stands behind the barriers of iteration 0): no global load, and so no wait on the
+        // operator loads in flight around it, where the tail runs
+        if constexpr (STAIL != 0) {
+            if (wave == 0) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s_s2[lane + 64 * j] = s2l.v[j];
+            }
+        }
     }
     // Tracker (vamp.py:22-26): xmmse = p, r = 0 (so r~ = p at t = 0), var(prev) = 1
     {
@@ -313,7 +331,9 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
             // complete during the gather's wait: through the per-phase kernel-argument pointer
             // they are not hoisted out of the loop (held across it, the values were spilled, and
             // vamp_advance waited on their scratch reload)
-            const S2Lane s2x = s2_lane(P, P.s + (size_t)ep * P.sch);
+            // (the split form reads them where its tail runs)
+            S2Lane s2x;
+            if constexpr (STAIL == 0) s2x = s2_lane(P, P.s + (size_t)ep * P.sch);
             const unsigned tag = P.gen * (unsigned)(P.max_iter + 1) + (unsigned)te + 1u;
             if (!part_gather(grs, ((unsigned)te * nwx + wg0) * 32u, P.wpe, tag, P.pbar + 1, g, scr, &s_flag)) return false;
             stamp(te, 6);
@@ -395,8 +415,12 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 g.maxabs = G;
                 fixed = (int)c;
             }
-        stamp(te, 9);   // (slot 9: vamp_advance starts)
-        nx = vamp_advance(P, cur, g, fixed, te, scr, &s2x);
+        if constexpr (STAIL != 0) {
+            nx = vamp_advance_head(P, cur, g, fixed, te);   // (slot 9: the tail's end, in iteration te + 1)
+        } else {
+            stamp(te, 9);   // (slot 9: vamp_advance starts)
+            nx = vamp_advance(P, cur, g, fixed, te, scr, &s2x);
+        }
         stamp(te, 7);
         return true;
     };
@@ -541,6 +565,21 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
         } else if constexpr (H2)
             gemm_h2<NC, G3>(sP, ldx, Wx1, cc0, cr, ci);
         else if constexpr (X3) {
+            if constexpr (STAIL != 0) {
+                // the tail of the record that drives this iteration (t >= 1; iteration 0's is whole:
+                // vamp_first_iter), complete before the w epilogue reads cur.vr: behind group 0's MFMAs
+                // and the request of group 1's operators
+                auto tail0 = [&](int g) __attribute__((always_inline)) {
+                    if (g == 0 && t > 0) {
+                        S2Lane s2x;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) s2x.v[j] = s_s2[lane + 64 * j];
+                        vamp_advance_tail(P, cur, s2x);
+                        stamp(t, 9);
+                    }
+                };
+                gemm_x3_ring<NC, G3, X3R, X3PIN, true, true>(sP, ldx, Wx1, cc0, wring, cr, ci, Wx2, X3NoHook(), tail0);
+            } else
             gemm_x3_ring<NC, G3, X3R, X3PIN, true, true>(sP, ldx, Wx1, cc0, wring, cr, ci, Wx2);
             // a building forward leaves q0 for the reuse forwards that follow it: row 0 (always a
             // valid trial) of workgroup 0, lanes 0-15 of every wave

@@ -3,10 +3,13 @@
 tests/test_gpu_vamp_ring_prefill.py (tests/golden/ring_prefill_bits.part<k>.npz).
 
   python tools/record_forward_bits.py [--out DIR] [--stem STEM] [--cases "Nt,Na,Nr,B,alphabet;..."] [--share-channel]
+                                      [--ebn0 "dB;..."]
 
 --stem / --cases record another fixture (tests/golden/<stem>.part<k>.npz) for another case list;
 --share-channel draws one channel, the first case's, stores it once ('shared/U', 's', 'Vh', 'SNR')
-and runs every case on it (the cases must agree in Nt and Nr).
+and runs every case that agrees with it in Nt and Nr on it (another case draws and stores its own);
+--ebn0 sets Eb/N0 per case (one value: every case; an empty entry: the alphabet's default) and
+stores that case's SNR as '<case>/SNR', e.g. to record a forward that stops before the cap.
 
 Public API only (Config, Channel, Data, VAMP, amp_native.prepare_counts), so the same script runs
 on any commit: a change that must leave the engine's results bit-identical is checked against a
@@ -45,9 +48,10 @@ def config(Nt, Na, Nr, B, alphabet, device):
                   channel_profile='uniform', channel_truncation='tail', device=device)
 
 
-def make_inputs(case, shared=None):
+def make_inputs(case, shared=None, ebn0=None):
     """One channel and two epochs of messages + noise (host tensors), in the reference's call order.
-    shared: the make_inputs result of another case whose channel (A, U, s, Vh, SNR) this one uses."""
+    shared: the make_inputs result of another case whose channel (A, U, s, Vh, SNR) this one uses;
+    ebn0: this case's own Eb/N0 (else the alphabet's default, or the shared channel's SNR)."""
     from channel import Channel
     from data import Data
     np.random.seed(SEED)
@@ -60,6 +64,8 @@ def make_inputs(case, shared=None):
         SNR = c.snr(EBN0[case[4]])
     else:
         A, U, s, Vh, SNR = (shared[k] for k in ('A', 'U', 's', 'Vh', 'SNR'))
+    if ebn0 is not None:
+        SNR = c.snr(ebn0)
     eps = []
     for _ in range(2):
         x, sym, idx = da.generate_message()
@@ -134,21 +140,31 @@ def main():
     ap.add_argument('--cases', default=None, help='"Nt,Na,Nr,B,alphabet;..." (default: CASES)')
     ap.add_argument('--share-channel', action='store_true',
                     help="one channel, the first case's, stored once and used by every case")
+    ap.add_argument('--ebn0', default=None, help='"dB;..." per case (one value: every case; empty: the default)')
     args = ap.parse_args()
     cases = CASES if args.cases is None else [
         tuple(int(v) for v in c.split(',')[:4]) + (c.split(',')[4],) for c in args.cases.split(';')]
+    ebn0 = [None] * len(cases)
+    if args.ebn0 is not None:
+        vals = args.ebn0.split(';')
+        vals = vals * len(cases) if len(vals) == 1 else vals
+        assert len(vals) == len(cases), (vals, cases)
+        ebn0 = [float(v) if v.strip() else None for v in vals]
     device = torch.device('cuda', 0)
     flat = {}
     shared = None
-    for case in cases:
+    for case, eb in zip(cases, ebn0):
         name = case_name(*case)
-        inp = make_inputs(case, shared)
+        own = shared is not None and case[0:3:2] != shared['dims']   # another Nt, Nr: its own channel
+        inp = make_inputs(case, None if own else shared, eb)
         res = run_case(case, inp, device)
         print(name, 'prepares (building, reuse) per forward:', [m for m, _ in res],
               'T:', [int(o['T'][0]) for _, o in res])
         if args.share_channel and shared is None:
-            shared = inp
-        chan = 'shared' if args.share_channel else name
+            shared = dict(inp, dims=case[0:3:2])
+        chan = 'shared' if args.share_channel and not own else name
+        if eb is not None:
+            flat[f'{name}/SNR'] = np.array([inp['SNR']], dtype=np.float64)
         if f'{chan}/U' not in flat:
             for k in ('U', 's', 'Vh'):
                 flat[f'{chan}/{k}'] = as_np(inp[k])

@@ -125,7 +125,13 @@ def main():
     print('iteration 0 (median cycles): ' + '  '.join(f'{name} {np.median(d[:, 0, i]):.0f}'
                                                        for i, name in enumerate(PHASES[:5])))
     raw = a[:nwg * iters * STRIDE].reshape(nwg, iters, STRIDE).astype(np.int64)[:, 1:Tn]
-    if Tn > 1 and np.all(raw[:, :, 9] > 0):   # slot 9: the start of vamp_advance (the scalars' own work)
+    if Tn > 1 and np.all(raw[:, :, 9] > 0) and np.all(raw[:, :, 9] < raw[:, :, 6]):
+        # vamp_advance in two parts (bf16x3, one workgroup per CU): slot 9 is the end of the tail, inside
+        # this iteration's GEMM1 (slot 1 -> slot 2); the scalars phase is the head alone
+        print(f'  scalars: head (gather end -> record) median {np.median(raw[:, :, 7] - raw[:, :, 6]):.0f} cycles; '
+              f'tail done median {np.median(raw[:, :, 9] - raw[:, :, 1]):.0f} cycles into GEMM1 '
+              f'(of {np.median(raw[:, :, 2] - raw[:, :, 1]):.0f})')
+    elif Tn > 1 and np.all(raw[:, :, 9] > 0):   # slot 9: the start of vamp_advance (the scalars' own work)
         print(f'  scalars: gather end -> advance start median {np.median(raw[:, :, 9] - raw[:, :, 6]):.0f}, '
               f'vamp_advance median {np.median(raw[:, :, 7] - raw[:, :, 9]):.0f} cycles')
     arrival_spread(a, st, nwg, iters, Tn)
