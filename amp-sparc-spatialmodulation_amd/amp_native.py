@@ -106,6 +106,7 @@ SIGNATURES = {
     'amp_vamp_workspace_bytes': (C.c_size_t, [_D, _I, _I]),
     'amp_vamp_select_engine': (C.c_int, [_D, _I, _I]),
     'amp_vamp_select_gemm': (C.c_int, [_D, _I, _I]),
+    'amp_vamp_select_gemm_k': (C.c_int, [_D, _I, _I, _I]),
     'amp_vamp2_workspace_bytes': (C.c_size_t, [_D, _I]),
     'amp_vamp2_run': (C.c_int, [_D, _K, C.POINTER(AmpVamp2Args), _P]),
     'amp_vamp_persist_trace': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), _P, _P]),

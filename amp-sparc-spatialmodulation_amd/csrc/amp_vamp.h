@@ -377,7 +377,7 @@ bool vamp_persist_eligible(const amp_dims* d, int k, int ncu, int epochs = 1, in
 int vamp_persist_max_epochs(const amp_dims* d, int k, int ncu, int gemm = AMP_GEMM_AUTO);
 int vamp_persist_wg_per_cu(const amp_dims* d, int k, int gemm);   // resident workgroups per CU of the launch
 int vamp_gemm_select(const amp_dims* d, int k, int gemm);   // 0 f32, 1 bf16x3, 2 fp16x2 (amp_vamp.hip)
-bool vamp_persist_x3_fits(int N, int k, int L);
+bool vamp_persist_x3_fits(int N, int k, int L, int K = 0);   // K: constellation size (0: at most 16 points)
 bool vamp_persist_ytil_in_kernel(const VampK& P);
 bool vamp_persist_ytil_h2(const VampK& P);
 int vamp_persist_launch(const VampK& P, const Const64& c64, const DecConst& dc, hipStream_t st, int ncu);

@@ -518,10 +518,10 @@ static int vamp_setup(const amp_dims* d, const amp_constellation* c, const amp_v
     P.c = to_const(c);
     c64 = to_const64(c);
     AMP_REQUIRE(a->gemm >= AMP_GEMM_AUTO && a->gemm <= AMP_GEMM_I8, "amp_vamp: gemm %d", a->gemm);
-    const bool x3_fits = vamp_persist_x3_fits(d->N, a->k, d->L);
+    const bool x3_fits = vamp_persist_x3_fits(d->N, a->k, d->L, c->K);
     AMP_REQUIRE((a->gemm != AMP_GEMM_X3 && a->gemm != AMP_GEMM_H2 && a->gemm != AMP_GEMM_I8) || x3_fits,
                 "amp_vamp: the split-precision engines need k == N, N %% 64 == 0 and "
-                "their LDS carve within 160 KB (N = %d, L = %d)", d->N, d->L);
+                "their LDS carve within 160 KB (N = %d, L = %d, K = %d)", d->N, d->L, c->K);
     P.x3 = vamp_gemm_mode(a->gemm, x3_fits);
     P.Wx1 = w.Wx1; P.Wx2 = w.Wx2;
     P.dump = debug_dump_ptr();
@@ -818,9 +818,11 @@ int amp_vamp_debug_prepare_counts(uint64_t* out) {
     return AMP_OK;
 }
 
-int amp_vamp_select_gemm(const amp_dims* d, int32_t k, int32_t gemm) {
-    if (!d || k <= 0 || gemm < AMP_GEMM_AUTO || gemm > AMP_GEMM_I8) return AMP_E_ARG;
-    const bool fits = vamp_persist_x3_fits(d->N, k, d->L);
+int amp_vamp_select_gemm(const amp_dims* d, int32_t k, int32_t gemm) { return amp_vamp_select_gemm_k(d, k, gemm, 0); }
+
+int amp_vamp_select_gemm_k(const amp_dims* d, int32_t k, int32_t gemm, int32_t K) {
+    if (!d || k <= 0 || gemm < AMP_GEMM_AUTO || gemm > AMP_GEMM_I8 || K < 0) return AMP_E_ARG;
+    const bool fits = vamp_persist_x3_fits(d->N, k, d->L, K);
     if ((gemm == AMP_GEMM_X3 || gemm == AMP_GEMM_H2 || gemm == AMP_GEMM_I8) && !fits) return AMP_E_ARG;
     static const int code[4] = {AMP_GEMM_F32, AMP_GEMM_X3, AMP_GEMM_H2, AMP_GEMM_I8};
     return code[vamp_gemm_mode(gemm, fits)];

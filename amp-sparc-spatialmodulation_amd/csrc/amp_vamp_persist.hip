@@ -67,8 +67,14 @@ bool vamp_persist_ytil_h2(const VampK& P) {
     return P.n == 2 * P.N && P.k == P.N && 2 * PBM * pl_ldx(P.n) <= playout(P.N, P.k, P.L, true).offV0;
 }
 
-bool vamp_persist_x3_fits(int N, int k, int L) {
-    return k == N && N % 64 == 0 && (size_t)playout(N, k, L, true).total * 4 + 2048 <= 160 * 1024;
+// K: the constellation size (0: not known, taken as at most 16 points).  Beside its dynamic carve
+// vamp_persist holds static LDS: up to 1.3 KB for the alphabets of at most 16 points, 4.8 KB with a
+// 64-point table (the streamed denoiser's points and the decision's).  With the 2 KB allowance for
+// every K, N = 256 at L = 64 passed for square 64-QAM and the launch then failed in
+// hipFuncSetAttribute; tests/test_persist_denoiser_cpu.py holds the code objects to these two figures.
+bool vamp_persist_x3_fits(int N, int k, int L, int K) {
+    const size_t fixed = K > 16 ? 5120 : 2048;
+    return k == N && N % 64 == 0 && (size_t)playout(N, k, L, true).total * 4 + fixed <= 160 * 1024;
 }
 
 // Workgroups per CU.  Two at N = 64 on the bf16x3 engine (its instantiation bounded for two

@@ -871,7 +871,12 @@ static int persist_launch_t(const VampK& P, const DecConst& dc, hipStream_t st) 
     if (attr_lds != lds) {
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
-            set_error("vamp_persist: hipFuncSetAttribute: %s", hipGetErrorString(e));
+            // (the carve plus this instantiation's static LDS beyond 160 KB: vamp_persist_x3_fits allows
+            // for the latter by a constant).  Taken off the runtime's last-error slot, or the caller's
+            // next HIP call reports it
+            (void)hipGetLastError();
+            set_error("vamp_persist: hipFuncSetAttribute: %s (%zu B of dynamic LDS, N = %d, L = %d, K = %d)",
+                      hipGetErrorString(e), lds, P.N, P.L, KK);
             return AMP_E_LAUNCH;
         }
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * NWV, lds);

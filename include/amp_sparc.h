@@ -153,6 +153,11 @@ int amp_vamp_select_engine(const amp_dims* d, int32_t k, int32_t engine);
 /* The arithmetic the persistent engine will use for this shape: AMP_GEMM_X3, AMP_GEMM_H2,
  * AMP_GEMM_I8 or AMP_GEMM_F32 (AMP_E_ARG when `gemm` is X3 / H2 / I8 and the shape does not fit). */
 int amp_vamp_select_gemm(const amp_dims* d, int32_t k, int32_t gemm);
+/* The same for a constellation of K points, as amp_vamp_run decides it: the kernels of a 64-point
+ * alphabet hold 3.5 KB more static LDS, so at N = 256 the split-precision engines take it up to
+ * L = 32 sections per trial only (L = 64 for K <= 16; AUTO then runs the f32 form).
+ * amp_vamp_select_gemm is K = 0: at most 16 points. */
+int amp_vamp_select_gemm_k(const amp_dims* d, int32_t k, int32_t gemm, int32_t K);
 /* Diagnostic: a persistent-engine forward that stamps s_memtime per workgroup, iteration and
  * phase into trace (device, nwg * max_iter * 10 + 4 * nwg uint64; layout in amp_vamp.hip). */
 int amp_vamp_persist_trace(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* trace,
