@@ -7,6 +7,10 @@ allclose early exit and the decision / counters run on the device; the Loss reso
 counters lazily, so consecutive epochs queue without a host stall.  The layer-level surface of
 the reference is kept too: ``Tracker(H, y, sigma2, config)`` + ``BAMPLayer.forward(T)``
 (amp_bamp_prepare / amp_bamp_iterate / amp_bamp_finalize).
+
+Shapes: M = Nt / Na a power of two and N = Nt Lin even; n = Nr Lout may be odd, N % 4 may be 2 and
+2N need not fill its last column tile (the library pads workspace arrays only: xmap, xmmse and var
+here stay dense [B, N]).  The split-precision tiles (GEMM_X3 / GEMM_H2) keep N % 64 == n % 64 == 0.
 """
 from __future__ import annotations
 

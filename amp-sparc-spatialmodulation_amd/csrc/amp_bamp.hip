@@ -41,6 +41,7 @@ struct BampK {
     int B, N, n, L, M, bn;
     int kapA1, ncpA1, kapA2, ncpA2, kapB1, ncpB1, kapB2, ncpB2;
     int nblk, max_iter;
+    int ild, sld;       // row strides of invu and s (bamp_ild / bamp_sld: n, 2n rounded up to 4)
     float sigma2;       // f32(noise_var): u = v + sigma2 (bamp.py:61)
     const float* Wabs2;    // [ncpA1][kapA1]   v = |H|^2 var
     const float* WH;       // [ncpA2][kapA2]   H xmmse
@@ -49,8 +50,8 @@ struct BampK {
     const float* y;        // [B][2n]
     float* v;              // [B][n]
     float* z;              // [B][2n]
-    float* invu;           // [B][n]
-    float* s;              // [B][2n]  (y - z)/u
+    float* invu;           // [B][ild]
+    float* s;              // [B][sld]  (y - z)/u
     float* cov;            // [B][N]
     float* xmap;           // [B][2N]  caller
     float* xm;             // [B][2N]  caller
@@ -148,6 +149,7 @@ static void bamp_geometry(const amp_dims* d, BampK& P) {
     P.kapB1 = round_up(d->n, GBK); P.ncpB1 = round_up(d->N, 128);
     P.kapB2 = round_up(2 * d->n, GBK); P.ncpB2 = round_up(2 * d->N, P.bn);
     P.nblk = cdiv(d->B, GBM) * (P.ncpB2 / P.bn);
+    P.ild = bamp_ild(d->n); P.sld = bamp_sld(d->n);
 }
 
 static BampWs bamp_carve(const amp_dims* d, int max_iter, void* base) {
@@ -164,8 +166,8 @@ static BampWs bamp_carve(const amp_dims* d, int max_iter, void* base) {
     w.WHH = cv.take<float>((size_t)P.ncpB2 * P.kapB2);
     w.v = cv.take<float>((size_t)d->B * d->n);
     w.z = cv.take<float>((size_t)d->B * 2 * d->n);
-    w.invu = cv.take<float>((size_t)d->B * d->n);
-    w.s = cv.take<float>((size_t)d->B * 2 * d->n);
+    w.invu = cv.take<float>((size_t)d->B * P.ild);
+    w.s = cv.take<float>((size_t)d->B * P.sld);
     w.cov = cv.take<float>((size_t)d->B * d->N);
     w.var1 = cv.take<float>((size_t)d->B * d->N);
     w.secmax = cv.take<float>((size_t)d->B * d->L);
@@ -199,8 +201,9 @@ __device__ __forceinline__ int bke(const BampK& P, int w, int cb) { return P.ban
 // KC: the A chunk of the f32 tile (GKC; 256 for the block-banded H, whose short reduction ranges
 // need no longer chunks: 33 KB of LDS, four tiles per CU instead of two; the fp16x2 tile only in
 // the GKC instantiations).  The chunking does not change the MFMA order: the same bits.
-// v = |H|^2 var (bamp.py:59)
-template <int KC = GKC, bool X3 = false>
+// v = |H|^2 var (bamp.py:59).  AL: var's loader (ALoadPair where N % 4 == 2: the caller's rows are
+// then only 8-byte aligned)
+template <int KC = GKC, bool X3 = false, class AL = ALoadPlain>
 __global__ __launch_bounds__(AMP_WG) void bamp_ka1(BampK P, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (P.iters[t].stopped) return;
@@ -212,8 +215,8 @@ __global__ __launch_bounds__(AMP_WG) void bamp_ka1(BampK P, int t) {
         gemm_tile_h2<128, false>(P.ap, P.rows_pad, P.rexp, P.N, P.Wabs2, BH2_EX, row0, col0, lds, bkb(P, 0, tile.cb),
                                        bke(P, 0, tile.cb));
     else
-        gemm_tile<128, ALoadPlain, KC>(ALoadPlain{bvar(P, t + 1), P.N, P.B, P.N}, P.Wabs2, P.kapA1, row0, col0, lds,
-                                       bkb(P, 0, tile.cb), bke(P, 0, tile.cb));
+        gemm_tile<128, AL, KC>(AL{bvar(P, t + 1), P.N, P.B, P.N}, P.Wabs2, P.kapA1, row0, col0, lds,
+                               bkb(P, 0, tile.cb), bke(P, 0, tile.cb));
     using C = GemmCfg<128>;
     for (int e = threadIdx.x; e < GBM * 128; e += AMP_WG) {
         const int rho = e >> 7, cc = e & 127;
@@ -249,7 +252,7 @@ __global__ __launch_bounds__(AMP_WG) void bamp_ka2(BampK P, int t) {
             yv[u] = *reinterpret_cast<const float2*>(P.y + oc);
             zv[u] = *reinterpret_cast<const float2*>(P.z + oc);
             vv[u] = P.v[o];
-            iuo[u] = P.invu[o];
+            iuo[u] = P.invu[(size_t)row * P.ild + i];
         }
     };
     if constexpr (X3)
@@ -268,7 +271,7 @@ __global__ __launch_bounds__(AMP_WG) void bamp_ka2(BampK P, int t) {
         const int rho = e >> 6, cp = e & 63;
         const int row = row0 + rho, i = (col0 >> 1) + cp;
         if (row < P.B && i < P.n) {
-            const size_t oc = (size_t)row * twon + 2 * i, o = (size_t)row * P.n + i;
+            const size_t oc = (size_t)row * twon + 2 * i;
             const float hr = lds[rho * C::LDC + 2 * cp], hi = lds[rho * C::LDC + 2 * cp + 1];
             const float yr = yv[u].x, yi = yv[u].y;
             const float vi = vv[u], iu_old = iuo[u];
@@ -277,8 +280,8 @@ __global__ __launch_bounds__(AMP_WG) void bamp_ka2(BampK P, int t) {
             const float uu = vi + P.sigma2;
             const float iu = 1.0f / uu;
             *reinterpret_cast<float2*>(P.z + oc) = make_float2(zr, zi);
-            P.invu[o] = iu;
-            *reinterpret_cast<float2*>(P.s + oc) = make_float2((yr - zr) * iu, (yi - zi) * iu);
+            P.invu[(size_t)row * P.ild + i] = iu;
+            *reinterpret_cast<float2*>(P.s + (size_t)row * P.sld + 2 * i) = make_float2((yr - zr) * iu, (yi - zi) * iu);
         }
     }
 }
@@ -296,7 +299,7 @@ __global__ __launch_bounds__(AMP_WG) void bamp_kb1(BampK P, int t) {
         gemm_tile_h2<128, false>(P.ap, P.rows_pad, P.rexp, P.n, P.Wabs2T, BH2_EX, row0, col0, lds, bkb(P, 2, tile.cb),
                                        bke(P, 2, tile.cb));
     else
-        gemm_tile<128, ALoadPlain, KC>(ALoadPlain{P.invu, P.n, P.B, P.n}, P.Wabs2T, P.kapB1, row0, col0, lds,
+        gemm_tile<128, ALoadPlain, KC>(ALoadPlain{P.invu, P.ild, P.B, P.ild}, P.Wabs2T, P.kapB1, row0, col0, lds,
                                        bkb(P, 2, tile.cb), bke(P, 2, tile.cb));
     using C = GemmCfg<128>;
     for (int e = threadIdx.x; e < GBM * 128; e += AMP_WG) {
@@ -346,14 +349,14 @@ __global__ __launch_bounds__(AMP_WG) void bamp_kb2(BampK P, Const64 c64, int t) 
     using C = GemmCfg<BN, KC>;
     const GemmTile tile = (KC == GKC && P.tile_rows) ? xcd_tile_rows() : xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    const int twoN = 2 * P.N, twon = 2 * P.n;
+    const int twoN = 2 * P.N;
     if constexpr (X3)
         gemm_tile_x3<BN, true>(P.ap, P.rows_pad, P.n, P.WHH, row0, col0, lds, bkb(P, 3, tile.cb), bke(P, 3, tile.cb));
     else if (KC == GKC && P.h2)
         gemm_tile_h2<BN, true>(P.ap, P.rows_pad, P.rexp, P.n, P.WHH, BH2_EX, row0, col0, lds, bkb(P, 3, tile.cb),
                                bke(P, 3, tile.cb));
     else
-        gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, twon, P.B, twon}, P.WHH, P.kapB2, row0, col0, lds,
+        gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, P.sld, P.B, P.sld}, P.WHH, P.kapB2, row0, col0, lds,
                                       bkb(P, 3, tile.cb), bke(P, 3, tile.cb));
     const int nrows = min(GBM, P.B - row0), ncols = min(BN, twoN - col0);
     float* sit = lds + C::CTILE_FLOATS + 2048;   // past the partial-store scratch
@@ -702,7 +705,11 @@ __global__ void bamp_init_kernel(BampK P) {
         }
         if (e < Bn) {
             reinterpret_cast<float2*>(P.z)[e] = reinterpret_cast<const float2*>(P.y)[e];
-            P.invu[e] = iu;
+            P.invu[P.ild == P.n ? e : (e / P.n) * P.ild + e % P.n] = iu;
+        }
+        if (e < (size_t)P.B) {   // the pads of the invu and s rows (bamp_ild / bamp_sld), zeroed once
+            for (int k = P.n; k < P.ild; ++k) P.invu[e * P.ild + k] = 0.f;
+            for (int k = 2 * P.n; k < P.sld; ++k) P.s[e * P.sld + k] = 0.f;
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -757,7 +764,8 @@ static bool bamp_short_chunks(const BampK& P) {
         const char* e = diag_env("AMP_BAMP_KC");
         return e && atoi(e) == 512;
     }();
-    return !P.h2 && !P.x3 && !off;
+    // N % 4 == 2: always (the pair loader is instantiated at the short chunk only)
+    return !P.h2 && !P.x3 && (!off || P.N % 4 != 0);
 }
 
 template <int KK>
@@ -827,12 +835,22 @@ namespace amp {
 
 // The parameter block of one BAMP forward from the C-ABI arguments (validated).
 static int bamp_setup(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a, BampK& P, Const64& c64) {
-    int rc = check_dims(d, c);
+    // any n and any even N (check_dims: M = Nt / Na a power of two); the column tiles take a partial
+    // last tile, invu and s padded row strides, var at N % 4 == 2 the pair loader
+    int rc = check_dims(d, c, true, true);
     if (rc) return rc;
+    AMP_REQUIRE(bamp_index_ok(d, d->B), "amp_bamp_run: B = %d trials of max(2N, 2n) = %d columns need more than "
+                "32-bit offsets (or more than 65535 column tiles)", d->B, 2 * std::max(d->N, d->n));
     AMP_REQUIRE(a && a->H && a->y && a->xmap && a->xmmse && a->var && a->status && a->ws,
                 "amp_bamp_run: null pointer argument");
     AMP_REQUIRE(a->max_iter > 0, "amp_bamp_run: max_iter must be positive");
-    AMP_REQUIRE(d->N % 4 == 0 && d->n % 4 == 0, "amp_bamp_run: N (%d) and n (%d) must be multiples of 4", d->N, d->n);
+    // every argument check before the workspace is carved (the arithmetic's comment: below)
+    AMP_REQUIRE(a->denoiser == 0 || a->denoiser == 1, "amp_bamp_run: denoiser %d", a->denoiser);
+    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32 || a->gemm == AMP_GEMM_H2 || a->gemm == AMP_GEMM_X3,
+                "amp_bamp_run: gemm %d (AUTO, F32, X3 or H2)", a->gemm);
+    const bool h2ok = bamp_h2_shape(d);
+    AMP_REQUIRE((a->gemm != AMP_GEMM_H2 && a->gemm != AMP_GEMM_X3) || h2ok,
+                "amp_bamp_run: the split-precision GEMMs need N %% 64 == 0 and n %% 64 == 0 (N = %d, n = %d)", d->N, d->n);
     const BampWs w = bamp_carve(d, a->max_iter, a->ws);
     AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_bamp_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
     rc = bamp_attrs();
@@ -853,7 +871,6 @@ static int bamp_setup(const amp_dims* d, const amp_constellation* c, const amp_b
         const bool band = (d->Lin > 1 || d->Lout > 1) && !(e && e[0] == '0');
         for (int i = 0; i < 4; ++i) P.band[i] = band ? w.band[i] : nullptr;
     }
-    AMP_REQUIRE(a->denoiser == 0 || a->denoiser == 1, "amp_bamp_run: denoiser %d", a->denoiser);
     P.elementwise = a->denoiser;
     P.P0 = a->P0;
     P.Ps = a->Ps;
@@ -861,11 +878,6 @@ static int bamp_setup(const amp_dims* d, const amp_constellation* c, const amp_b
     // asked for: AMP_GEMM_F32 (f32 MFMA), AMP_GEMM_X3 (bf16x3 tiles, 24-bit operands) or, only when
     // asked for (AMP_GEMM_H2, or AUTO with AMP_BAMP_GEMM=h2), the fp16x2 tile (22-bit operands:
     // narrower than the reference).  AUTO: f32 MFMA (AMP_BAMP_GEMM=x3: bf16x3 where the shape tiles).
-    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32 || a->gemm == AMP_GEMM_H2 || a->gemm == AMP_GEMM_X3,
-                "amp_bamp_run: gemm %d (AUTO, F32, X3 or H2)", a->gemm);
-    const bool h2ok = bamp_h2_shape(d);
-    AMP_REQUIRE((a->gemm != AMP_GEMM_H2 && a->gemm != AMP_GEMM_X3) || h2ok,
-                "amp_bamp_run: the split-precision GEMMs need N %% 64 == 0 and n %% 64 == 0 (N = %d, n = %d)", d->N, d->n);
     static const char gemm_env = [] {
         const char* e = diag_env("AMP_BAMP_GEMM");
         return e ? e[0] : '\0';
@@ -967,18 +979,20 @@ static void bamp_gemms(const BampK& P, const Const64& c64, int t, hipStream_t st
     // the host reads bvar(P, t + 1) as the device does: (t + 1) & 1 picks var1, else var0
     if (P.h2 || P.x3) bamp_split(P, ((t + 1) & 1) ? P.var1 : P.var0, P.N, P.N, false, t, st);
     const bool skc = bamp_short_chunks(P);
-    if (skc) hipLaunchKernelGGL((bamp_ka1<256>), dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), BSKC_LDS, st, P, t);
+    if (skc && P.N % 4 != 0)
+        hipLaunchKernelGGL((bamp_ka1<256, false, ALoadPair>), dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), BSKC_LDS, st, P, t);
+    else if (skc) hipLaunchKernelGGL((bamp_ka1<256>), dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), BSKC_LDS, st, P, t);
     else if (P.x3) hipLaunchKernelGGL((bamp_ka1<GKC, true>), dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), XLDS_R, st, P, t);
     else hipLaunchKernelGGL((bamp_ka1<>), dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), BLDS, st, P, t);
     if (P.h2 || P.x3) bamp_split(P, P.xm, 2 * P.N, P.N, true, t, st);
     if (skc) hipLaunchKernelGGL((bamp_ka2<256>), dim3(gr, P.ncpA2 / 128), dim3(AMP_WG), BSKC_LDS, st, P, t);
     else if (P.x3) hipLaunchKernelGGL((bamp_ka2<GKC, true>), dim3(gr, P.ncpA2 / 128), dim3(AMP_WG), XLDS_C, st, P, t);
     else hipLaunchKernelGGL((bamp_ka2<>), dim3(gr, P.ncpA2 / 128), dim3(AMP_WG), BLDS, st, P, t);
-    if (P.h2 || P.x3) bamp_split(P, P.invu, P.n, P.n, false, t, st);
+    if (P.h2 || P.x3) bamp_split(P, P.invu, P.ild, P.n, false, t, st);
     if (skc) hipLaunchKernelGGL((bamp_kb1<256>), dim3(gr, P.ncpB1 / 128), dim3(AMP_WG), BSKC_LDS, st, P, t);
     else if (P.x3) hipLaunchKernelGGL((bamp_kb1<GKC, true>), dim3(gr, P.ncpB1 / 128), dim3(AMP_WG), XLDS_R, st, P, t);
     else hipLaunchKernelGGL((bamp_kb1<>), dim3(gr, P.ncpB1 / 128), dim3(AMP_WG), BLDS, st, P, t);
-    if (P.h2 || P.x3) bamp_split(P, P.s, 2 * P.n, P.n, true, t, st);
+    if (P.h2 || P.x3) bamp_split(P, P.s, P.sld, P.n, true, t, st);
     launch_kb2(P, c64, gr, t, st);
 }
 

@@ -29,6 +29,7 @@ struct TBampK {
     int E, N, n, L, M, bn;
     int kapA1, ncpA1, kapA2, ncpA2, kapB1, ncpB1, kapB2, ncpB2;
     int nct, max_iter;
+    int ild, sld;          // row strides of invu and s (bamp_ild / bamp_sld: n, 2n rounded up to 4)
     float sigma2;          // f32(noise_var): u = v + sigma2 (bamp.py:61)
     const float* Wabs2;    // [ncpA1][kapA1]   v = |H|^2 var
     const float* WH;       // [ncpA2][kapA2]   H xmmse
@@ -37,8 +38,8 @@ struct TBampK {
     const float* y;        // [E][2n]
     float* v;              // [E][n]
     float* z;              // [E][2n]
-    float* invu;           // [E][n]
-    float* s;              // [E][2n]  (y - z)/u
+    float* invu;           // [E][ild]
+    float* s;              // [E][sld]  (y - z)/u
     float* cov;            // [E][N]
     float* xmap;           // [E][2N]  caller
     float* xm;             // [E][2N]  caller
@@ -72,6 +73,7 @@ static void tbamp_geometry(const amp_dims* d, int E, TBampK& P) {
     P.kapB1 = round_up(d->n, GBK); P.ncpB1 = round_up(d->N, 128);
     P.kapB2 = round_up(2 * d->n, GBK); P.ncpB2 = round_up(2 * d->N, P.bn);
     P.nct = P.ncpB2 / P.bn;
+    P.ild = bamp_ild(d->n); P.sld = bamp_sld(d->n);
 }
 
 static TBampWs tbamp_carve(const amp_dims* d, int E, void* base) {
@@ -85,8 +87,8 @@ static TBampWs tbamp_carve(const amp_dims* d, int E, void* base) {
     w.WHH = cv.take<float>((size_t)P.ncpB2 * P.kapB2);
     w.v = cv.take<float>((size_t)E * d->n);
     w.z = cv.take<float>((size_t)E * 2 * d->n);
-    w.invu = cv.take<float>((size_t)E * d->n);
-    w.s = cv.take<float>((size_t)E * 2 * d->n);
+    w.invu = cv.take<float>((size_t)E * P.ild);
+    w.s = cv.take<float>((size_t)E * P.sld);
     w.cov = cv.take<float>((size_t)E * d->N);
     w.var1 = cv.take<float>((size_t)E * d->N);
     w.secmax = cv.take<float>((size_t)E * d->L);
@@ -109,7 +111,8 @@ __device__ __forceinline__ int tbke(const TBampK& P, int w, int cb) { return P.b
 
 // KC: the A chunk of the f32 tile, as amp_bamp.hip launches it (256 at the narrow column tile);
 // the chunking does not change the MFMA order: the same bits.
-// v = |H|^2 var (bamp.py:59)
+// v = |H|^2 var (bamp.py:59).  AL: var's loader (ALoadPair where N % 4 == 2, as bamp_ka1)
+template <class AL>
 __global__ __launch_bounds__(AMP_WG) void tbamp_ka1(TBampK P, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_stop[GBM];
@@ -117,8 +120,8 @@ __global__ __launch_bounds__(AMP_WG) void tbamp_ka1(TBampK P, int t) {
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
     if (!tile_rows_live(P.iters, row0, P.E, s_stop)) return;
-    gemm_tile<128, ALoadPlain, 256>(ALoadPlain{tbvar(P, t + 1), P.N, P.E, P.N}, P.Wabs2, P.kapA1, row0, col0, lds,
-                                    tbkb(P, 0, tile.cb), tbke(P, 0, tile.cb));
+    gemm_tile<128, AL, 256>(AL{tbvar(P, t + 1), P.N, P.E, P.N}, P.Wabs2, P.kapA1, row0, col0, lds,
+                            tbkb(P, 0, tile.cb), tbke(P, 0, tile.cb));
     using C = GemmCfg<128, 256>;
     for (int e = threadIdx.x; e < GBM * 128; e += AMP_WG) {
         const int rho = e >> 7, cc = e & 127;
@@ -152,7 +155,7 @@ __global__ __launch_bounds__(AMP_WG) void tbamp_ka2(TBampK P, int t) {
         yv[u] = *reinterpret_cast<const float2*>(P.y + oc);
         zv[u] = *reinterpret_cast<const float2*>(P.z + oc);
         vv[u] = P.v[o];
-        iuo[u] = P.invu[o];
+        iuo[u] = P.invu[(size_t)row * P.ild + i];
     }
 #pragma unroll
     for (int u = 0; u < IT; ++u) {
@@ -160,7 +163,7 @@ __global__ __launch_bounds__(AMP_WG) void tbamp_ka2(TBampK P, int t) {
         const int rho = e >> 6, cp = e & 63;
         const int row = row0 + rho, i = (col0 >> 1) + cp;
         if (row < P.E && i < P.n && !s_stop[rho]) {
-            const size_t oc = (size_t)row * twon + 2 * i, o = (size_t)row * P.n + i;
+            const size_t oc = (size_t)row * twon + 2 * i;
             const float hr = lds[rho * C::LDC + 2 * cp], hi = lds[rho * C::LDC + 2 * cp + 1];
             const float yr = yv[u].x, yi = yv[u].y;
             const float vi = vv[u], iu_old = iuo[u];
@@ -169,8 +172,8 @@ __global__ __launch_bounds__(AMP_WG) void tbamp_ka2(TBampK P, int t) {
             const float uu = vi + P.sigma2;
             const float iu = 1.0f / uu;
             *reinterpret_cast<float2*>(P.z + oc) = make_float2(zr, zi);
-            P.invu[o] = iu;
-            *reinterpret_cast<float2*>(P.s + oc) = make_float2((yr - zr) * iu, (yi - zi) * iu);
+            P.invu[(size_t)row * P.ild + i] = iu;
+            *reinterpret_cast<float2*>(P.s + (size_t)row * P.sld + 2 * i) = make_float2((yr - zr) * iu, (yi - zi) * iu);
         }
     }
 }
@@ -183,7 +186,7 @@ __global__ __launch_bounds__(AMP_WG) void tbamp_kb1(TBampK P, int t) {
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
     if (!tile_rows_live(P.iters, row0, P.E, s_stop)) return;
-    gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.invu, P.n, P.E, P.n}, P.Wabs2T, P.kapB1, row0, col0, lds,
+    gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.invu, P.ild, P.E, P.ild}, P.Wabs2T, P.kapB1, row0, col0, lds,
                                     tbkb(P, 2, tile.cb), tbke(P, 2, tile.cb));
     using C = GemmCfg<128, 256>;
     for (int e = threadIdx.x; e < GBM * 128; e += AMP_WG) {
@@ -232,8 +235,8 @@ __global__ __launch_bounds__(AMP_WG) void tbamp_kb2(TBampK P, int t) {
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
     if (!tile_rows_live(P.iters, row0, P.E, s_stop)) return;
-    const int twoN = 2 * P.N, twon = 2 * P.n;
-    gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, twon, P.E, twon}, P.WHH, P.kapB2, row0, col0, lds,
+    const int twoN = 2 * P.N;
+    gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, P.sld, P.E, P.sld}, P.WHH, P.kapB2, row0, col0, lds,
                                   tbkb(P, 3, tile.cb), tbke(P, 3, tile.cb));
     const int nrows = min(GBM, P.E - row0), ncols = min(BN, twoN - col0);
     float* sit = lds + C::CTILE_FLOATS + 2048;   // past the partial-store scratch
@@ -360,9 +363,14 @@ __global__ void tbamp_init_kernel(TBampK P) {
         }
         if (e < En) {
             reinterpret_cast<float2*>(P.z)[e] = reinterpret_cast<const float2*>(P.y)[e];
-            P.invu[e] = iu;
+            P.invu[P.ild == P.n ? e : (e / P.n) * P.ild + e % P.n] = iu;
         }
-        if (e < (size_t)P.E) P.iters[e] = TBampIter{0, 0, 0, 0};
+        if (e < (size_t)P.E) {
+            P.iters[e] = TBampIter{0, 0, 0, 0};
+            // the pads of the invu and s rows (bamp_ild / bamp_sld), zeroed once
+            for (int k = P.n; k < P.ild; ++k) P.invu[e * P.ild + k] = 0.f;
+            for (int k = 2 * P.n; k < P.sld; ++k) P.s[e * P.sld + k] = 0.f;
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *P.nstop = 0u;
 }
@@ -428,15 +436,15 @@ size_t amp_bamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int3
 
 int amp_bamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
                         const amp_trials_decide_args* dec, int32_t trials, void* stream) {
-    int rc = check_dims(d, c);
+    int rc = check_dims(d, c, true, true);   // any n, any even N, a partial last column tile (amp_bamp_run)
     if (rc) return rc;
     AMP_REQUIRE(d->B == 1, "amp_bamp_trials_run: dims describe ONE trial (B = %d, must be 1)", d->B);
     AMP_REQUIRE(trials >= 1, "amp_bamp_trials_run: trials = %d", trials);
+    AMP_REQUIRE(bamp_index_ok(d, trials), "amp_bamp_trials_run: %d trials of max(2N, 2n) = %d columns need more "
+                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
     AMP_REQUIRE(a && a->H && a->y && a->xmap && a->xmmse && a->var && a->status && a->ws,
                 "amp_bamp_trials_run: null pointer argument");
     AMP_REQUIRE(a->max_iter > 0, "amp_bamp_trials_run: max_iter must be positive");
-    AMP_REQUIRE(d->N % 4 == 0 && d->n % 4 == 0, "amp_bamp_trials_run: N (%d) and n (%d) must be multiples of 4", d->N,
-                d->n);
     AMP_REQUIRE(a->denoiser == 0, "amp_bamp_trials_run: the element-wise denoiser ('random' mode) has no "
                 "independent-trial form");
     AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "amp_bamp_trials_run: f32 GEMMs only (gemm %d)",
@@ -480,7 +488,10 @@ int amp_bamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp
     AMP_LAUNCH_CHECK("tbamp_init");
     const int gr = cdiv(E, GBM);
     for (int t = 0; t < P.max_iter; ++t) {
-        hipLaunchKernelGGL(tbamp_ka1, dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, t);
+        if (P.N % 4 != 0)
+            hipLaunchKernelGGL(tbamp_ka1<ALoadPair>, dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, t);
+        else
+            hipLaunchKernelGGL(tbamp_ka1<ALoadPlain>, dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, t);
         hipLaunchKernelGGL(tbamp_ka2, dim3(gr, P.ncpA2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, t);
         hipLaunchKernelGGL(tbamp_kb1, dim3(gr, P.ncpB1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, t);
         tbamp_launch_kb2(P, gr, t, st);

@@ -157,6 +157,25 @@ struct ALoadPlain {
     }
 };
 
+// The same for rows that are only 8-byte aligned: lda and ka even but no multiples of 4 (BAMP's
+// var, the caller's dense [B][N], at N % 4 == 2; ka >= 2).  Two float2 loads per staged float4,
+// each at its own clamped address; the staged values are ALoadPlain's, so the tile's bits do not
+// depend on the loader.
+struct ALoadPair {
+    const float* __restrict__ a;
+    int lda, rows, ka;
+    struct Raw { float2 lo, hi; };
+    __device__ __forceinline__ Raw raw(int row, int k) const {
+        const float* p = a + (size_t)min(row, rows - 1) * lda;
+        return Raw{*reinterpret_cast<const float2*>(p + min(k, ka - 2)),
+                   *reinterpret_cast<const float2*>(p + min(k + 2, ka - 2))};
+    }
+    __device__ __forceinline__ float4 fin(const Raw& v, int row, int k) const {
+        const bool lo = row < rows && k < ka, hi = row < rows && k + 2 < ka;
+        return make_float4(lo ? v.lo.x : 0.f, lo ? v.lo.y : 0.f, hi ? v.hi.x : 0.f, hi ? v.hi.y : 0.f);
+    }
+};
+
 // Computes the C tile of rows [row0, row0+32) x cols [col0, col0+BN) into `lds` (as the C
 // tile, row stride GemmCfg<BN>::LDC).  `wp` is the MFMA-packed [Ncp][kap] weight,
 // kap % GBK == 0, col0 % BN == 0, col0 + BN <= Ncp.  [kb, ke): the reduction range that holds

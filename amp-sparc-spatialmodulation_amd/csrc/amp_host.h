@@ -172,7 +172,7 @@ int call_allreduce_hook(double* buf, int count, int op, hipStream_t st);
 int hook_failure(const char* what);   // sets the error text, returns AMP_E_LAUNCH
 
 // tail_tile: the caller's column tiles take a partial last tile (2N % bn != 0 with 2N > bn) and its
-// GEMM operands an odd n (SCAMP: scamp_sld)
+// GEMM operands an odd n (SCAMP: scamp_sld; BAMP: bamp_ild / bamp_sld)
 int check_dims(const amp_dims* d, const amp_constellation* c, bool tiled = true, bool tail_tile = false);
 int device_cu_count();   // compute units of the current device (cached)
 // amp_stream_create_cu_range's registry (amp_weights.hip): the CU range of a stream it made, and the
@@ -224,6 +224,22 @@ inline bool section_bn_wide_env() {
     return v;
 }
 inline int section_bn(const amp_dims* d) { return (2 * d->M <= 128 && !section_bn_wide_env()) ? 128 : 256; }
+
+// BAMP (amp_bamp.hip, amp_bamp_trials.hip): row strides of the two workspace arrays that are A
+// operands of a GEMM, 1/u [rows][n] (kb1) and s = (y - z)/u [rows][2n] (kb2), rounded up to the
+// tile's float4 loads (amp_gemm.h ALoadPlain).  The pad floats are zeroed once by the init kernels
+// and never written again; the operators' reduction rows beyond n / 2n are zero.  n % 4 == 0: the
+// dense strides.  y, z, v, cov, xmap, xmmse and var keep their dense strides (var, the caller's, is
+// staged through ALoadPair where N % 4 == 2).
+inline int bamp_ild(int n) { return (n + 3) & ~3; }
+inline int bamp_sld(int n) { return (2 * n + 3) & ~3; }
+// The kernels index trials x columns and sections with 32-bit products and the GEMM grids put the
+// column tiles on gridDim.y: shapes beyond either are refused, never wrapped (as scamp_index_ok;
+// the packed operators' offsets are 64-bit throughout).
+inline bool bamp_index_ok(const amp_dims* d, int rows) {
+    const long long cols = 2LL * (d->N > d->n ? d->N : d->n);
+    return cols <= 0x7fffffffLL / 2 && (long long)rows * (cols + 4) <= 0x7fffffffLL && cols / 128 + 1 <= 65535;
+}
 
 // Expanded-weight builders (amp_weights.hip)
 enum { WPACK_NONE = 0, WPACK32 = 1, WPACK16 = 2, WPACKX3 = 3, WPACKH2 = 4, WPACKH2_ABS2 = 5, WPACKI8 = 6, WPACKX3_ABS2 = 7 };

@@ -355,19 +355,30 @@ typedef struct amp_bamp_args {
     int32_t pad;
 } amp_bamp_args;
 
+/* Shapes (amp_bamp_run, _run_sharded, _prepare / _iterate / _finalize and amp_bamp_trials_run, with
+ * the f32 tiles): M = Nt / Na a power of two <= 128, N = Nt Lin even (N % 4 may be 2), n = Nr Lout
+ * any positive integer (odd included), 2N any multiple of 2M (the column tiles take a partial last
+ * tile), Lin, Lh >= 1 (block-banded H), B >= 1, both denoisers.  a->var, a->xmap, a->xmmse and y stay
+ * dense; only workspace arrays are padded (amp_bamp_workspace_bytes accounts for them; shapes with
+ * N % 4 == 0 and n % 4 == 0 report the bytes and return the bits they did before).  AMP_E_ARG with a
+ * message: M no power of two, N odd, B (or trials) x max(2N, 2n) beyond 32-bit offsets or more than
+ * 65535 column tiles, and AMP_GEMM_X3 / AMP_GEMM_H2 unless N % 64 == 0 and n % 64 == 0.  Every check of
+ * an argument precedes the first use of a pointer. */
 size_t amp_bamp_workspace_bytes(const amp_dims* d, int32_t max_iter);
 int amp_bamp_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a, void* stream);
 /* amp_bamp_run on one rank's slice of a trial-sharded batch (amp_vamp_run_sharded's protocol,
  * the hook of amp_set_allreduce_hook): max|xi| / min section max (bamp.py:70) and the allclose
  * count (bamp.py:140) all-reduced per iteration; decision on xmap with amp_map_decide_count_rows.
- * denoiser 0 only (the element-wise mode runs at B = 1). */
+ * denoiser 0 only (the element-wise mode runs at B = 1).  Shapes: as amp_bamp_run, for this rank's
+ * d->B rows. */
 int amp_bamp_run_sharded(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a, int32_t B_global,
                          void* stream);
 /* Layer-level pieces of amp_bamp_run (same arguments; amp_bamp_run = prepare, iterate(t) for
  * t < max_iter, finalize): prepare = Tracker (bamp.py:13-25: the H / H^H / |H|^2 operators,
  * xmmse = 0, var = 1, z = y, u = sigma2); iterate(t) = one BAMPLayer.forward (bamp.py:48-64) +
  * the allclose(var) early exit of bamp.py:140 (a device-side no-op once it has fired);
- * finalize = the executed iterations' var into a->var and the status record. */
+ * finalize = the executed iterations' var into a->var and the status record.  Shapes: as
+ * amp_bamp_run (the same checks in each call). */
 int amp_bamp_prepare(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a, void* stream);
 int amp_bamp_iterate(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a, int32_t t, void* stream);
 int amp_bamp_finalize(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a, void* stream);
@@ -522,7 +533,9 @@ typedef struct amp_trials_decide_args {
 size_t amp_vamp_trials_workspace_bytes(const amp_dims* d, int32_t k, int32_t max_iter, int32_t trials);
 int amp_vamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
                         const amp_trials_decide_args* dec, int32_t trials, void* stream);
-/* replaces `trials` calls of BAMP.forward at B = 1 (bamp.py:116-143) + Loss.error_rate */
+/* replaces `trials` calls of BAMP.forward at B = 1 (bamp.py:116-143) + Loss.error_rate.  Shapes: as
+ * amp_bamp_run (odd n, N % 4 == 2, a partial last column tile), f32 GEMMs and denoiser 0 only; trials x
+ * max(2N, 2n) within 32-bit offsets. */
 size_t amp_bamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials);
 int amp_bamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
                         const amp_trials_decide_args* dec, int32_t trials, void* stream);
