@@ -172,7 +172,7 @@ int call_allreduce_hook(double* buf, int count, int op, hipStream_t st);
 int hook_failure(const char* what);   // sets the error text, returns AMP_E_LAUNCH
 
 // tail_tile: the caller's column tiles take a partial last tile (2N % bn != 0 with 2N > bn) and its
-// GEMM operands an odd n (SCAMP: scamp_sld; BAMP: bamp_ild / bamp_sld)
+// GEMM operands an odd n (SCAMP: scamp_sld; BAMP: bamp_ild / bamp_sld; VAMP: vamp_wld, ALoadPair on y)
 int check_dims(const amp_dims* d, const amp_constellation* c, bool tiled = true, bool tail_tile = false);
 int device_cu_count();   // compute units of the current device (cached)
 // amp_stream_create_cu_range's registry (amp_weights.hip): the CU range of a stream it made, and the
@@ -240,6 +240,15 @@ inline bool bamp_index_ok(const amp_dims* d, int rows) {
     const long long cols = 2LL * (d->N > d->n ? d->N : d->n);
     return cols <= 0x7fffffffLL / 2 && (long long)rows * (cols + 4) <= 0x7fffffffLL && cols / 128 + 1 <= 65535;
 }
+
+// VAMP launch engines (amp_vamp.hip, amp_vamp_trials.hip): row stride of w [rows][2k], the
+// workspace array that is GEMM2's A operand, rounded up to the tile's float4 loads (2k at even k).
+// The pad floats are zeroed once by the init kernels and never written again; Wt2's reduction rows
+// beyond 2k are zero.  ytil, s2, secmax, r, xmmse and var keep their dense strides (2N % 4 == 0: N is
+// even); y, the caller's [rows][2n], is staged through ALoadPair at odd n (gemm_store).
+inline int vamp_wld(int k) { return (2 * k + 3) & ~3; }
+// 32-bit products and gridDim.y, as bamp_index_ok: refused beyond, never wrapped.
+inline bool vamp_index_ok(const amp_dims* d, int rows) { return bamp_index_ok(d, rows); }
 
 // Expanded-weight builders (amp_weights.hip)
 enum { WPACK_NONE = 0, WPACK32 = 1, WPACK16 = 2, WPACKX3 = 3, WPACKH2 = 4, WPACKH2_ABS2 = 5, WPACKI8 = 6, WPACKX3_ABS2 = 7 };

@@ -26,7 +26,7 @@ struct VampK {
     const float* s;     // singular values (f32 [k])
     float* s2;          // s**2 (vamp.py:17)
     float* ytil;        // [B][2k]
-    float* w;           // [B][2k]
+    float* w;           // [B][wld]  (wld = vamp_wld(k): 2k rounded up to 4, the pad zero)
     float* r;           // [B][2N]  (caller's r)
     float* xm;          // [B][2N]  (caller's xmmse)
     float* var0;        // [B][N] caller's var: var of even iterations
@@ -85,6 +85,7 @@ struct VampK {
     // running the GEMM.  Two words, each read at its own place in the loop.
     float* q0;
     int q0_store, q0_load;
+    int wld;            // row stride of w (vamp_wld; the persistent engines keep w in LDS)
     Const c;
 };
 
@@ -114,6 +115,13 @@ static void vamp_geometry(const amp_dims* d, int k, VampK& P) {
     P.bn2 = section_bn(d);
     P.kap2 = round_up(2 * k, GBK); P.ncp2 = round_up(2 * d->N, P.bn2);
     P.nblk2 = cdiv(d->B, GBM) * (P.ncp2 / P.bn2);
+    P.wld = vamp_wld(k);
+}
+
+// The shape part of vamp_persist_eligible: only then can a persistent engine run, and only then
+// does the workspace hold its operator buffers (Wq0 / Wq1 / Wq2, Wx1 / Wx2).
+inline bool vamp_persist_shape(const amp_dims* d, int k) {
+    return k == d->N && (d->N == 64 || d->N == 128 || d->N == 256);
 }
 
 // chans: channel-dependent operator sets (Wq0 / Wx1 / Wx2) to hold — one per epoch for side-by-side
@@ -128,18 +136,22 @@ static VampWs vamp_carve(const amp_dims* d, int k, int max_iter, void* base, int
     w.Wt2 = cv.take<float>((size_t)P.ncp2 * P.kap2);
     w.s2 = cv.take<float>((size_t)k);
     w.ytil = cv.take<float>((size_t)d->B * 2 * k);
-    w.w = cv.take<float>((size_t)d->B * 2 * k);
+    w.w = cv.take<float>((size_t)d->B * P.wld);
     w.var1 = cv.take<float>((size_t)d->B * d->N);
     w.secmax = cv.take<float>((size_t)d->B * d->L);
     w.secabs = cv.take<float>((size_t)d->B * d->L);
     w.parts = cv.take<Partial>((size_t)max_iter * P.nblk2);
     w.iters = cv.take<VampIter>((size_t)max_iter + 1);
     const int nwg = cdiv(d->B, 16);
-    w.Wq0 = cv.take<float>((size_t)2 * k * 2 * d->n * chans);
-    w.Wq1 = cv.take<float>((size_t)2 * k * 2 * d->N);
-    w.Wq2 = cv.take<float>((size_t)2 * d->N * 2 * k);
-    w.Wx1 = cv.take<float>((size_t)3 * k * d->N * chans);      // 6 bf16 per complex entry
-    w.Wx2 = cv.take<float>((size_t)3 * k * d->N * chans);
+    // the persistent engines' operators: no launch-engine path reads them (10.5 -> 3.9 GB at the
+    // reference's published Nt = 1344 shape); every shape that can reach a persistent engine keeps
+    // its bytes and offsets
+    const bool pe = vamp_persist_shape(d, k);
+    w.Wq0 = pe ? cv.take<float>((size_t)2 * k * 2 * d->n * chans) : nullptr;
+    w.Wq1 = pe ? cv.take<float>((size_t)2 * k * 2 * d->N) : nullptr;
+    w.Wq2 = pe ? cv.take<float>((size_t)2 * d->N * 2 * k) : nullptr;
+    w.Wx1 = pe ? cv.take<float>((size_t)3 * k * d->N * chans) : nullptr;      // 6 bf16 per complex entry
+    w.Wx2 = pe ? cv.take<float>((size_t)3 * k * d->N * chans) : nullptr;
     w.pxch = cv.take<double>((size_t)max_iter * nwg * 4);
     w.pbar = cv.take<unsigned>(PBAR_WORDS);                  // barrier words (zeroed per launch); the
     w.pparts = cv.take<Partial>((size_t)max_iter * nwg);     // granules carry generation tags

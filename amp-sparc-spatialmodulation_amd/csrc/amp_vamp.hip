@@ -88,8 +88,7 @@ __global__ __launch_bounds__(AMP_WG) void vamp_k1(VampK P, int t) {
         if (row < P.B && col < twok) {
             const float q = lds[rho * C::LDC + cc];
             const float sc = 1.0f / (s2v[u] + it.vr);
-            const size_t o = (size_t)row * twok + col;
-            P.w[o] = sc * (yv[u] + it.vr * q) - q;
+            P.w[(size_t)row * P.wld + col] = sc * (yv[u] + it.vr * q) - q;
         }
     }
 }
@@ -132,8 +131,8 @@ __global__ __launch_bounds__(AMP_WG) void vamp_k2(VampK P, int t) {
     using C = GemmCfg<BN>;
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    const int twoN = 2 * P.N, twok = 2 * P.k;
-    gemm_tile<BN>(ALoadPlain{P.w, twok, P.B, twok}, P.Wt2, P.kap2, row0, col0, lds);
+    const int twoN = 2 * P.N;
+    gemm_tile<BN>(ALoadPlain{P.w, P.wld, P.B, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
     // x~ = V w + r~ ; r = (x~ - alpha r~) / (1 - alpha)   (vamp.py:72, 79)
     const int nrows = min(GBM, P.B - row0), ncols = min(BN, twoN - col0);
     {
@@ -420,6 +419,8 @@ __global__ void vamp_init_kernel(VampK P) {
         reinterpret_cast<float2*>(P.xm)[e] = make_float2(p, 0.f);
         reinterpret_cast<float2*>(P.r)[e] = make_float2(0.f, 0.f);
         P.var1[e] = 1.0f;
+        if (e < (size_t)P.B)   // the pad of w's rows (vamp_wld), zeroed once: vamp_k1 stores columns < 2k only
+            for (int j = 2 * P.k; j < P.wld; ++j) P.w[e * P.wld + j] = 0.f;
     }
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P.k; i += gridDim.x * blockDim.x) P.s2[i] = P.s[i] * P.s[i];
 }
@@ -482,13 +483,23 @@ int vamp_gemm_select(const amp_dims* d, int k, int gemm) {
 
 static int vamp_setup(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, VampK& P, Const64& c64,
                       int chans = 1) {
-    int rc = check_dims(d, c);
+    // any n, any k <= min(n, N) and any even N (check_dims: M = Nt / Na a power of two): the column
+    // tiles take a partial last tile, w a padded row stride (vamp_wld), y at odd n the pair loader
+    int rc = check_dims(d, c, true, true);
     if (rc) return rc;
-    AMP_REQUIRE(a && a->U && a->s && a->Vh && a->y && a->r && a->xmmse && a->var && a->status && a->ws,
+    AMP_REQUIRE(a, "amp_vamp: null pointer argument");
+    AMP_REQUIRE(vamp_index_ok(d, d->B), "amp_vamp: B = %d trials of max(2N, 2n) = %d columns need more than 32-bit "
+                "offsets (or more than 65535 column tiles)", d->B, 2 * std::max(d->N, d->n));
+    AMP_REQUIRE(a->U && a->s && a->Vh && a->y && a->r && a->xmmse && a->var && a->status && a->ws,
                 "amp_vamp: null pointer argument");
-    AMP_REQUIRE(a->k > 0 && a->k <= d->N && a->k <= d->n && a->k % 2 == 0, "amp_vamp: k = %d must be min(n, N), even",
-                a->k);
+    AMP_REQUIRE(a->k > 0 && a->k <= d->N && a->k <= d->n, "amp_vamp: k = %d must be min(n, N)", a->k);
     AMP_REQUIRE(a->max_iter > 0, "amp_vamp: max_iter must be positive");
+    // every argument check before the workspace is carved
+    AMP_REQUIRE(a->gemm >= AMP_GEMM_AUTO && a->gemm <= AMP_GEMM_I8, "amp_vamp: gemm %d", a->gemm);
+    const bool x3_fits = vamp_persist_x3_fits(d->N, a->k, d->L, c->K);
+    AMP_REQUIRE((a->gemm != AMP_GEMM_X3 && a->gemm != AMP_GEMM_H2 && a->gemm != AMP_GEMM_I8) || x3_fits,
+                "amp_vamp: the split-precision engines need k == N, N %% 64 == 0 and "
+                "their LDS carve within 160 KB (N = %d, L = %d, K = %d)", d->N, d->L, c->K);
     const VampWs w = vamp_carve(d, a->k, a->max_iter, a->ws, chans);
     AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_vamp: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
     vamp_geometry(d, a->k, P);
@@ -517,11 +528,6 @@ static int vamp_setup(const amp_dims* d, const amp_constellation* c, const amp_v
     P.trace = nullptr;
     P.c = to_const(c);
     c64 = to_const64(c);
-    AMP_REQUIRE(a->gemm >= AMP_GEMM_AUTO && a->gemm <= AMP_GEMM_I8, "amp_vamp: gemm %d", a->gemm);
-    const bool x3_fits = vamp_persist_x3_fits(d->N, a->k, d->L, c->K);
-    AMP_REQUIRE((a->gemm != AMP_GEMM_X3 && a->gemm != AMP_GEMM_H2 && a->gemm != AMP_GEMM_I8) || x3_fits,
-                "amp_vamp: the split-precision engines need k == N, N %% 64 == 0 and "
-                "their LDS carve within 160 KB (N = %d, L = %d, K = %d)", d->N, d->L, c->K);
     P.x3 = vamp_gemm_mode(a->gemm, x3_fits);
     P.Wx1 = w.Wx1; P.Wx2 = w.Wx2;
     P.dump = debug_dump_ptr();

@@ -116,7 +116,7 @@ int vamp_persist_wg_per_cu(const amp_dims* d, int k, int gemm) {
 
 int vamp_persist_max_epochs(const amp_dims* d, int k, int ncu, int gemm) {
     const int gemm_mode = vamp_gemm_select(d, k, gemm);
-    if (k != d->N || !(d->N == 64 || d->N == 128 || d->N == 256) || d->M > 64) return 0;
+    if (!vamp_persist_shape(d, k) || d->n % 2 != 0 || d->M > 64) return 0;   // odd n: the launch engine
     if ((size_t)playout(d->N, k, d->L).total * 4 + 2048 > 160 * 1024) return 0;
     const int wpe = cdiv(d->B, PBM);
     if (wpe > ncu) return 0;
@@ -125,7 +125,7 @@ int vamp_persist_max_epochs(const amp_dims* d, int k, int ncu, int gemm) {
 }
 
 bool vamp_persist_eligible(const amp_dims* d, int k, int ncu, int epochs, int gemm) {
-    if (k != d->N || !(d->N == 64 || d->N == 128 || d->N == 256) || d->M > 64) return false;
+    if (!vamp_persist_shape(d, k) || d->n % 2 != 0 || d->M > 64) return false;   // odd n: the launch engine
     if (epochs < 1 || (epochs > 1 && d->B % PBM != 0)) return false;
     if (cdiv(d->B, PBM) > ncu ||
         (long)epochs * cdiv(d->B, PBM) > (long)persist_wg_cap(d->N, vamp_gemm_select(d, k, gemm)) * ncu)

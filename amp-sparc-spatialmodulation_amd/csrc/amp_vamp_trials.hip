@@ -48,7 +48,7 @@ static TVampWs tvamp_carve(const amp_dims* d, int k, int E, void* base) {
     w.Wt2 = cv.take<float>((size_t)P.ncp2 * P.kap2);
     w.s2 = cv.take<float>((size_t)k);
     w.ytil = cv.take<float>((size_t)E * 2 * k);
-    w.w = cv.take<float>((size_t)E * 2 * k);
+    w.w = cv.take<float>((size_t)E * P.wld);
     w.var1 = cv.take<float>((size_t)E * d->N);
     w.secmax = cv.take<float>((size_t)E * d->L);
     w.secabs = cv.take<float>((size_t)E * d->L);
@@ -70,6 +70,8 @@ __global__ __launch_bounds__(256) void tvamp_init_kernel(VampK P, unsigned* nsto
         reinterpret_cast<float2*>(P.xm)[e] = make_float2(p, 0.f);
         reinterpret_cast<float2*>(P.r)[e] = make_float2(0.f, 0.f);
         P.var1[e] = 1.0f;
+        if (e < (size_t)P.B)   // the pad of w's rows (vamp_wld), zeroed once: tvamp_k1 stores columns < 2k only
+            for (int j = 2 * P.k; j < P.wld; ++j) P.w[e * P.wld + j] = 0.f;
     }
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P.k; i += gridDim.x * blockDim.x) P.s2[i] = P.s[i] * P.s[i];
     if (blockIdx.x == 0) {
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(AMP_WG) void tvamp_k1(VampK P, const unsigned* nsto
             const float vr = s_it[rho].vr;
             const float q = lds[rho * C::LDC + cc];
             const float sc = 1.0f / (s2v[u] + vr);
-            P.w[(size_t)row * twok + col] = sc * (yv[u] + vr * q) - q;
+            P.w[(size_t)row * P.wld + col] = sc * (yv[u] + vr * q) - q;
         }
     }
 }
@@ -191,8 +193,8 @@ __global__ __launch_bounds__(AMP_WG) void tvamp_k2(VampK P, int t, const unsigne
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
     if (!tvamp_tile_records(P, row0, s_it)) return;
-    const int twoN = 2 * P.N, twok = 2 * P.k;
-    gemm_tile<BN>(ALoadPlain{P.w, twok, P.B, twok}, P.Wt2, P.kap2, row0, col0, lds);
+    const int twoN = 2 * P.N;
+    gemm_tile<BN>(ALoadPlain{P.w, P.wld, P.B, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
     // x~ = V w + r~ ; r = (x~ - alpha_e r~) / (1 - alpha_e)   (vamp.py:72, 79)
     const int nrows = min(GBM, P.B - row0), ncols = min(BN, twoN - col0);
     {
@@ -385,14 +387,15 @@ size_t amp_vamp_trials_workspace_bytes(const amp_dims* d, int32_t k, int32_t max
 
 int amp_vamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
                         const amp_trials_decide_args* dec, int32_t trials, void* stream) {
-    int rc = check_dims(d, c);
+    int rc = check_dims(d, c, true, true);   // any n, any k, any even N, a partial last column tile (amp_vamp_run)
     if (rc) return rc;
     AMP_REQUIRE(d->B == 1, "amp_vamp_trials_run: dims describe ONE trial (B = %d, must be 1)", d->B);
     AMP_REQUIRE(trials >= 1, "amp_vamp_trials_run: trials = %d", trials);
+    AMP_REQUIRE(vamp_index_ok(d, trials), "amp_vamp_trials_run: %d trials of max(2N, 2n) = %d columns need more "
+                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
     AMP_REQUIRE(a && a->U && a->s && a->Vh && a->y && a->r && a->xmmse && a->var && a->status && a->ws,
                 "amp_vamp_trials_run: null pointer argument");
-    AMP_REQUIRE(a->k > 0 && a->k <= d->N && a->k <= d->n && a->k % 2 == 0,
-                "amp_vamp_trials_run: k = %d must be min(n, N), even", a->k);
+    AMP_REQUIRE(a->k > 0 && a->k <= d->N && a->k <= d->n, "amp_vamp_trials_run: k = %d must be min(n, N)", a->k);
     AMP_REQUIRE(a->max_iter > 0, "amp_vamp_trials_run: max_iter must be positive");
     AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES,
                 "amp_vamp_trials_run: the persistent engine has no independent-trial form");

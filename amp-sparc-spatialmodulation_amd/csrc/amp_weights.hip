@@ -354,15 +354,16 @@ int set_lds_attr(const void* fn) {
 template int set_lds_attr<128>(const void*);
 template int set_lds_attr<256>(const void*);
 
-// Plain GEMM: C[rows][ldc] = A[rows][lda](ka valid) . Wt^T, columns [0, nc) stored.
-template <int BN>
+// Plain GEMM: C[rows][ldc] = A[rows][lda](ka valid) . Wt^T, columns [0, nc) stored.  AL: A's loader
+// (ALoadPair where its rows are only 8-byte aligned: VAMP's y at odd n)
+template <int BN, class AL = ALoadPlain>
 __global__ __launch_bounds__(AMP_WG) void gemm_store_kernel(const float* __restrict__ a, int lda, int rows, int ka,
                                                             const float* __restrict__ wt, int kap,
                                                             float* __restrict__ c, int ldc, int nc) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    gemm_tile<BN>(ALoadPlain{a, lda, rows, ka}, wt, kap, row0, col0, lds);
+    gemm_tile<BN>(AL{a, lda, rows, ka}, wt, kap, row0, col0, lds);
     using C = GemmCfg<BN>;
     for (int e = threadIdx.x; e < GBM * BN; e += AMP_WG) {
         const int rho = e / BN, cc = e % BN;
@@ -475,10 +476,19 @@ int gemm_store(const float* a, int lda, int rows, int ka, const float* wt, int k
     static bool attr = false;
     if (!attr) {
         int rc = set_lds_attr<128>((const void*)gemm_store_kernel<128>);
+        if (!rc) rc = set_lds_attr<128>((const void*)gemm_store_kernel<128, ALoadPair>);
         if (rc) return rc;
         attr = true;
     }
     dim3 grid(cdiv(rows, GBM), ncp / 128);
+    // rows of lda % 4 == 2 floats (or ka % 4 == 2 valid ones): the pair loader, the same staged values
+    AMP_REQUIRE(lda % 2 == 0 && ka % 2 == 0 && ka >= 2, "gemm_store: lda %d / ka %d must be even", lda, ka);
+    if (lda % 4 != 0 || ka % 4 != 0) {
+        hipLaunchKernelGGL((gemm_store_kernel<128, ALoadPair>), grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a, lda,
+                           rows, ka, wt, kap, c, ldc, nc);
+        AMP_LAUNCH_CHECK("gemm_store");
+        return AMP_OK;
+    }
     hipLaunchKernelGGL(gemm_store_kernel<128>, grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a, lda, rows, ka, wt,
                        kap, c, ldc, nc);
     AMP_LAUNCH_CHECK("gemm_store");

@@ -5,6 +5,12 @@
 signature and returns its own reused ``Loss`` (vamp.py:187-191).  The whole
 iteration loop, the allclose early exit and the decision/counting run on the device;
 the host reads back one 128-byte record per forward.
+
+Shapes: M = Nt / Na a power of two <= 128 and N = Nt Lin even; n = Nr Lout and k = min(n, N) may be
+odd and 2N need not fill its last column tile (launch engines, f32 tiles: forward, forward_trials,
+ShardedVAMP, Tracker / VAMPLayer; the library pads workspace arrays only: r, xmmse and var here stay
+dense [B, N]).  The persistent engine keeps k == N in {64, 128, 256} with an even n, the
+split-precision arithmetics k == N and N % 64 == 0.
 """
 from __future__ import annotations
 

@@ -167,11 +167,22 @@ int amp_vamp_persist_trace(const amp_dims* d, const amp_constellation* c, const 
  * how many launches were timed and their mean duration in ms, and clears the record. */
 int amp_debug_persist_timing(int32_t on);
 int amp_debug_persist_time(int32_t* n, float* mean_ms);
+/* Shapes (amp_vamp_run on the launch engine, amp_vamp_prepare / _iterate / _finalize,
+ * amp_vamp_run_sharded and amp_vamp_trials_run, f32 tiles): M = Nt / Na a power of two <= 128, N
+ * even; any n = Nr Lout (odd included), any k <= min(n, N) (odd included) and any 2N (a partial
+ * last column tile); rows x (2 max(N, n) + 4) must stay within 32-bit offsets (AMP_E_ARG with a
+ * message otherwise).  y, r, xmmse and var stay dense [rows][n] / [rows][N] at every shape: only
+ * the workspace's w rows are padded, and amp_vamp_workspace_bytes accounts for them.  The
+ * persistent engine needs k == N in {64, 128, 256} and an even n; the split-precision arithmetics
+ * (AMP_GEMM_X3 / _H2 / _I8) k == N, N % 64 == 0; amp_vamp2_run an even n and 2N within one column
+ * tile or a multiple of it.  The workspace holds the persistent engines' operator buffers only where
+ * k == N in {64, 128, 256}. */
 size_t amp_vamp_workspace_bytes(const amp_dims* d, int32_t k, int32_t max_iter);
 int amp_vamp_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* stream);
 /* Layer-level pieces of amp_vamp_run: prepare = Tracker (vamp.py:13-28);
  * iterate(t) = one VAMPLayer.forward + the allclose test of vamp.py:185 (no-op once stopped);
- * finalize = iteration count and NaN bookkeeping for the returned Loss. */
+ * finalize = iteration count and NaN bookkeeping for the returned Loss.  Shapes: as amp_vamp_run
+ * on the launch engine (odd n, odd k and a partial last column tile included). */
 int amp_vamp_prepare(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* stream);
 int amp_vamp_iterate(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, int32_t t, void* stream);
 int amp_vamp_finalize(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* stream);
@@ -281,7 +292,8 @@ int amp_vamp_shard_reset(void* xbuf, void* stream);
 int amp_vamp_detect_count_shard(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
                                 const amp_vamp_decide_args* dec, const amp_vamp_shard* sh, void* stream);
 /* amp_vamp_run on this rank's slice (launch engine) with the batch scalars all-reduced; workspace
- * as amp_vamp_workspace_bytes(d, ...) for the slice.  Decide with amp_map_decide_count_rows. */
+ * as amp_vamp_workspace_bytes(d, ...) for the slice.  Decide with amp_map_decide_count_rows.
+ * Shapes: as amp_vamp_run on the launch engine, for this rank's rows. */
 int amp_vamp_run_sharded(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, int32_t B_global,
                          void* stream);
 
@@ -529,7 +541,9 @@ typedef struct amp_trials_decide_args {
     int32_t rule;         /* AMP_RULE_SPARC / AMP_RULE_SEGMENTED */
     void* counts;         /* out amp_counts[trials] (device) */
 } amp_trials_decide_args;
-/* replaces `trials` calls of VAMP.forward at B = 1 (vamp.py:159-187) + Loss.error_rate */
+/* replaces `trials` calls of VAMP.forward at B = 1 (vamp.py:159-187) + Loss.error_rate.  Shapes: as
+ * amp_vamp_run on the launch engine (any n, any k <= min(n, N), any even N, any 2N), trials x
+ * (2 max(N, n) + 4) within 32-bit offsets. */
 size_t amp_vamp_trials_workspace_bytes(const amp_dims* d, int32_t k, int32_t max_iter, int32_t trials);
 int amp_vamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
                         const amp_trials_decide_args* dec, int32_t trials, void* stream);
