@@ -7,12 +7,13 @@
 //   xmmse, var = denoiser(xmap, tau = cov/2)  (bamp.py:66-77)
 // and the allclose(var) early exit (bamp.py:140).
 // Per iteration: four fp32-MFMA GEMM launches with fused epilogues + one reduction /
-// exact-float64 fix-up workgroup (same scheme as amp_vamp.hip).
+// exact-float64 fix-up workgroup (same scheme as amp_vamp.hip).  The parameter block and the
+// epilogues are amp_bamp.h's, shared with the independent-trial engine (amp_bamp_trials.hip): a
+// GEMM kernel here is its entry guard, the tile of its arithmetic and one epilogue call.
 #include <algorithm>
 #include <mutex>
 
-#include "amp_denoise.h"
-#include "amp_gemm.h"
+#include "amp_bamp.h"
 #include "amp_gemm_h2.h"
 #include "amp_gemm_x3.h"
 #include <vector>
@@ -22,64 +23,6 @@
 namespace amp {
 
 constexpr int BRWG = 1024;
-
-// bamp_ka2's epilogue loads issued before the GEMM (A/B builds): measured slower, cfg5 64-QAM
-// 18.24 -> 18.52 ms, ISI BAMP 0.1330 -> 0.1345 ms per iteration (same box, gpurun_out r5pf; the
-// 48 registers they hold across the reduction cost more than the overlap gains)
-
-struct alignas(16) BampIter {
-    int32_t stopped, T, fixed, fixed_all;
-    // exact float64 fix-up of iteration T-1 pending (set by bamp_r, done and settled by
-    // bamp_fixall): the exact batch max |xi| G, the float32 estimate's slack, the allclose count
-    // before the fix-up
-    double G, slack;
-    uint32_t notclose;
-    int32_t active, pad[2];
-};
-
-struct BampK {
-    int B, N, n, L, M, bn;
-    int kapA1, ncpA1, kapA2, ncpA2, kapB1, ncpB1, kapB2, ncpB2;
-    int nblk, max_iter;
-    int ild, sld;       // row strides of invu and s (bamp_ild / bamp_sld: n, 2n rounded up to 4)
-    float sigma2;       // f32(noise_var): u = v + sigma2 (bamp.py:61)
-    const float* Wabs2;    // [ncpA1][kapA1]   v = |H|^2 var
-    const float* WH;       // [ncpA2][kapA2]   H xmmse
-    const float* Wabs2T;   // [ncpB1][kapB1]   |H|^2^T (1/u)
-    const float* WHH;      // [ncpB2][kapB2]   H^H s
-    const float* y;        // [B][2n]
-    float* v;              // [B][n]
-    float* z;              // [B][2n]
-    float* invu;           // [B][ild]
-    float* s;              // [B][sld]  (y - z)/u
-    float* cov;            // [B][N]
-    float* xmap;           // [B][2N]  caller
-    float* xm;             // [B][2N]  caller
-    float* var0;           // caller's var (even iterations)
-    float* var1;           // workspace  (odd iterations)
-    float* secmax;         // [B*L] per-section max logit (fast path)
-    float* secabs;         // [B*L] per-section max |logit|
-    Partial* parts;        // [max_iter][nblk]
-    BampIter* iters;       // [max_iter + 1]
-    amp_status* status;
-    // block-banded H (Lin > 1 or Lout > 1): per column tile of Wabs2 / WH / Wabs2T / WHH the
-    // reduction range holding its nonzero blocks (weight_kband), else null (whole range)
-    const int* band[4];
-    XState* xs;            // trial-sharded exchange words (amp_bamp_run_sharded)
-    Const c;
-    int elementwise;                       // random_denoiser (bamp.py:79-88) instead of the block one
-    float P0, Ps;
-    // fp16x2 GEMMs (amp_gemm_h2.h): the four operators h2-packed into the weight buffers above
-    // (real |H|^2 two planes, complex H / H^H four), each GEMM's A rows split into `ap` first
-    // bf16x3 GEMMs (amp_gemm_x3.h, x3 = 1): the same scheme with three bf16 pieces per value (real
-    // |H|^2 three planes, complex H / H^H six; no exponents)
-    int h2, x3, rows_pad;
-    int tile_rows;         // row-block-major tile order (xcd_tile_rows: the fp16x2 tiles), else xcd_tile
-    unsigned short* ap;    // [4 planes][rows_pad][max(N, n)] fp16, or [6 planes][...] bf16
-    int* rexp;             // [rows_pad] row exponents
-    // launch engine: rcnt[1] is bamp_fixall's arrival counter (zeroed by bamp_init_kernel)
-    unsigned* rcnt;
-};
 
 // BAMP's fp16x2 operator scale exponent (the opt-in AMP_GEMM_H2 form): every operator piece is
 // scaled by 2^10, so |H|^2 must stay below 64 (|H| < 8; the channel's entries are ~CN(0, 1/Nr));
@@ -141,20 +84,9 @@ struct BampWs {
     size_t bytes;
 };
 
-static void bamp_geometry(const amp_dims* d, BampK& P) {
-    P.B = d->B; P.N = d->N; P.n = d->n; P.L = d->L; P.M = d->M;
-    P.bn = section_bn(d);
-    P.kapA1 = round_up(d->N, GBK); P.ncpA1 = round_up(d->n, 128);
-    P.kapA2 = round_up(2 * d->N, GBK); P.ncpA2 = round_up(2 * d->n, 128);
-    P.kapB1 = round_up(d->n, GBK); P.ncpB1 = round_up(d->N, 128);
-    P.kapB2 = round_up(2 * d->n, GBK); P.ncpB2 = round_up(2 * d->N, P.bn);
-    P.nblk = cdiv(d->B, GBM) * (P.ncpB2 / P.bn);
-    P.ild = bamp_ild(d->n); P.sld = bamp_sld(d->n);
-}
-
 static BampWs bamp_carve(const amp_dims* d, int max_iter, void* base) {
     BampK P;
-    bamp_geometry(d, P);
+    bamp_geometry(d, d->B, P);
     Carve cv(base);
     BampWs w;
     // the split forms' shapes also hold the bf16x3 real operators: three 16-bit planes, 1.5x the
@@ -192,12 +124,6 @@ static BampWs bamp_carve(const amp_dims* d, int max_iter, void* base) {
     return w;
 }
 
-__device__ __forceinline__ float* bvar(const BampK& P, int t) { return (t & 1) ? P.var1 : P.var0; }
-// reduction range of column tile cb of GEMM weight w (0..3: Wabs2, WH, Wabs2T, WHH); whole range
-// when the channel is not block-banded
-__device__ __forceinline__ int bkb(const BampK& P, int w, int cb) { return P.band[w] ? P.band[w][2 * cb] : 0; }
-__device__ __forceinline__ int bke(const BampK& P, int w, int cb) { return P.band[w] ? P.band[w][2 * cb + 1] : -1; }
-
 // KC: the A chunk of the f32 tile (GKC; 256 for the block-banded H, whose short reduction ranges
 // need no longer chunks: 33 KB of LDS, four tiles per CU instead of two; the fp16x2 tile only in
 // the GKC instantiations).  The chunking does not change the MFMA order: the same bits.
@@ -217,12 +143,7 @@ __global__ __launch_bounds__(AMP_WG) void bamp_ka1(BampK P, int t) {
     else
         gemm_tile<128, AL, KC>(AL{bvar(P, t + 1), P.N, P.B, P.N}, P.Wabs2, P.kapA1, row0, col0, lds,
                                bkb(P, 0, tile.cb), bke(P, 0, tile.cb));
-    using C = GemmCfg<128>;
-    for (int e = threadIdx.x; e < GBM * 128; e += AMP_WG) {
-        const int rho = e >> 7, cc = e & 127;
-        const int row = row0 + rho, col = col0 + cc;
-        if (row < P.B && col < P.n) P.v[(size_t)row * P.n + col] = lds[rho * C::LDC + cc];
-    }
+    bamp_store_v(P, AllRows{}, lds, row0, col0);
 }
 
 // z = H xmmse - v (y - z) / u ; u = v + sigma2 ; s = (y - z) / u   (bamp.py:60-63)
@@ -232,29 +153,7 @@ __global__ __launch_bounds__(AMP_WG) void bamp_ka2(BampK P, int t) {
     if (P.iters[t].stopped) return;
     const GemmTile tile = (KC == GKC && P.tile_rows) ? xcd_tile_rows() : xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
-    const int twoN = 2 * P.N, twon = 2 * P.n;
-    // every global load of this thread's epilogue elements before any store (the z / invu / s
-    // stores may alias the next element's loads as far as the compiler knows: one memory latency
-    // per element otherwise); each element reads and writes only its own z and invu (so the loads
-    // may also go before the GEMM: measured slower, round 5)
-    constexpr int IT = GBM * 64 / AMP_WG;
-    float2 yv[IT], zv[IT];
-    float vv[IT], iuo[IT];
-    auto epi_loads = [&] {
-#pragma unroll
-        for (int u = 0; u < IT; ++u) {
-            // unconditional loads at a clamped index (a lane-divergent branch around them
-            // serialises their latencies, amp_gemm.h ALoadPlain); out-of-range elements are never stored
-            const int e = threadIdx.x + u * AMP_WG;
-            const int rho = e >> 6, cp = e & 63;           // complex column pair
-            const int row = min(row0 + rho, P.B - 1), i = min((col0 >> 1) + cp, P.n - 1);
-            const size_t oc = (size_t)row * twon + 2 * i, o = (size_t)row * P.n + i;
-            yv[u] = *reinterpret_cast<const float2*>(P.y + oc);
-            zv[u] = *reinterpret_cast<const float2*>(P.z + oc);
-            vv[u] = P.v[o];
-            iuo[u] = P.invu[(size_t)row * P.ild + i];
-        }
-    };
+    const int twoN = 2 * P.N;
     if constexpr (X3)
         gemm_tile_x3<128, true>(P.ap, P.rows_pad, P.N, P.WH, row0, col0, lds, bkb(P, 1, tile.cb), bke(P, 1, tile.cb));
     else if (KC == GKC && P.h2)
@@ -263,27 +162,7 @@ __global__ __launch_bounds__(AMP_WG) void bamp_ka2(BampK P, int t) {
     else
         gemm_tile<128, ALoadPlain, KC>(ALoadPlain{P.xm, twoN, P.B, twoN}, P.WH, P.kapA2, row0, col0, lds,
                                        bkb(P, 1, tile.cb), bke(P, 1, tile.cb));
-    using C = GemmCfg<128>;
-    epi_loads();
-#pragma unroll
-    for (int u = 0; u < IT; ++u) {
-        const int e = threadIdx.x + u * AMP_WG;
-        const int rho = e >> 6, cp = e & 63;
-        const int row = row0 + rho, i = (col0 >> 1) + cp;
-        if (row < P.B && i < P.n) {
-            const size_t oc = (size_t)row * twon + 2 * i;
-            const float hr = lds[rho * C::LDC + 2 * cp], hi = lds[rho * C::LDC + 2 * cp + 1];
-            const float yr = yv[u].x, yi = yv[u].y;
-            const float vi = vv[u], iu_old = iuo[u];
-            const float zr = hr - (vi * (yr - zv[u].x)) * iu_old;
-            const float zi = hi - (vi * (yi - zv[u].y)) * iu_old;
-            const float uu = vi + P.sigma2;
-            const float iu = 1.0f / uu;
-            *reinterpret_cast<float2*>(P.z + oc) = make_float2(zr, zi);
-            P.invu[(size_t)row * P.ild + i] = iu;
-            *reinterpret_cast<float2*>(P.s + (size_t)row * P.sld + 2 * i) = make_float2((yr - zr) * iu, (yi - zi) * iu);
-        }
-    }
+    bamp_residual(P, AllRows{}, lds, row0, col0);
 }
 
 // cov = 1 / (|H|^2^T (1/u))   (bamp.py:62)
@@ -301,45 +180,8 @@ __global__ __launch_bounds__(AMP_WG) void bamp_kb1(BampK P, int t) {
     else
         gemm_tile<128, ALoadPlain, KC>(ALoadPlain{P.invu, P.ild, P.B, P.ild}, P.Wabs2T, P.kapB1, row0, col0, lds,
                                        bkb(P, 2, tile.cb), bke(P, 2, tile.cb));
-    using C = GemmCfg<128>;
-    for (int e = threadIdx.x; e < GBM * 128; e += AMP_WG) {
-        const int rho = e >> 7, cc = e & 127;
-        const int row = row0 + rho, col = col0 + cc;
-        if (row < P.B && col < P.N) P.cov[(size_t)row * P.N + col] = 1.0f / lds[rho * C::LDC + cc];
-    }
+    bamp_store_cov(P, AllRows{}, lds, row0, col0);
 }
-
-struct BampDenoisePolicy {
-    const float* tile;
-    const float* itile;   // LDS [32][ldi]: 1 / (cov / 2) of the tile's positions (bamp_kb2's xmap pass)
-    int ldc, ldi, spr, M, N, row0, colc0;
-    float* xm;
-    float* var_new;
-    const float* var_prev;
-    float* secmax;
-    float* secabs;
-    int L;
-    __device__ __forceinline__ void load(int sec, int m, float& rr, float& ri, float& it) const {
-        const int rho = sec / spr, sj = sec - rho * spr;
-        const float2 v = *reinterpret_cast<const float2*>(tile + rho * ldc + 2 * (sj * M + m));
-        rr = v.x; ri = v.y;
-        it = itile[rho * ldi + sj * M + m];   // 1 / tau, tau = cov / 2 (bamp.py:68)
-    }
-    __device__ __forceinline__ void store(int sec, int m, float xr, float xi, float var, PartAcc& pa) const {
-        const int rho = sec / spr, sj = sec - rho * spr;
-        const size_t o = (size_t)(row0 + rho) * N + colc0 + sj * M + m;
-        *reinterpret_cast<float2*>(xm + 2 * o) = make_float2(xr, xi);
-        var_new[o] = var;
-        pa.sumvar += (double)var;
-        pa.notclose += torch_close(var, var_prev[o]) ? 0u : 1u;     // bamp.py:140
-    }
-    __device__ __forceinline__ void section(int sec, float smax, float sabs) const {
-        const int rho = sec / spr, sj = sec - rho * spr;
-        const size_t o = (size_t)(row0 + rho) * L + (colc0 / M) + sj;
-        secmax[o] = smax;
-        secabs[o] = sabs;
-    }
-};
 
 // xmap = xmmse + cov (H^H s) ; xmmse, var = denoiser(xmap, cov/2)   (bamp.py:63-64)
 template <int BN, int KK, int KC = GKC, bool X3 = false>
@@ -359,39 +201,8 @@ __global__ __launch_bounds__(AMP_WG) void bamp_kb2(BampK P, Const64 c64, int t) 
         gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, P.sld, P.B, P.sld}, P.WHH, P.kapB2, row0, col0, lds,
                                       bkb(P, 3, tile.cb), bke(P, 3, tile.cb));
     const int nrows = min(GBM, P.B - row0), ncols = min(BN, twoN - col0);
-    float* sit = lds + C::CTILE_FLOATS + 2048;   // past the partial-store scratch
-    {
-        // the loads of this thread's elements before the xmap stores (which may alias them as far
-        // as the compiler knows)
-        constexpr int IT = GBM * BN / AMP_WG;
-        static_assert(C::CTILE_FLOATS + 2048 + GBM * (BN / 2) <= C::A_FLOATS, "1 / tau tile");
-        float xv[IT], cvv[IT];
-#pragma unroll
-        for (int u = 0; u < IT; ++u) {
-            // unconditional loads at a clamped index (see bamp_ka2); out-of-range elements unused
-            const int e = threadIdx.x + u * AMP_WG, rho = min(e / BN, nrows - 1), cc = min(e % BN, ncols - 1);
-            xv[u] = P.xm[(size_t)(row0 + rho) * twoN + col0 + cc];
-            cvv[u] = P.cov[(size_t)(row0 + rho) * P.N + ((col0 + cc) >> 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < IT; ++u) {
-            const int e = threadIdx.x + u * AMP_WG, rho = e / BN, cc = e % BN;
-            if (rho < nrows && cc < ncols) {
-                const size_t o = (size_t)(row0 + rho) * twoN + col0 + cc;
-                const float xp = xv[u] + cvv[u] * lds[rho * C::LDC + cc];
-                P.xmap[o] = xp;
-                lds[rho * C::LDC + cc] = xp;
-                // the denoiser's 1 / tau of this position, read from LDS there instead of a global
-                // load per position inside its loop (the same float32 operations)
-                if ((cc & 1) == 0) sit[rho * (BN / 2) + (cc >> 1)] = 1.0f / (cvv[u] * 0.5f);
-            }
-        }
-    }
-    __syncthreads();
-    BampDenoisePolicy pol;
-    pol.tile = lds; pol.itile = sit; pol.ldi = BN / 2; pol.ldc = C::LDC; pol.M = P.M; pol.N = P.N; pol.L = P.L;
-    pol.spr = (ncols / 2) / P.M; pol.row0 = row0; pol.colc0 = col0 / 2;
-    pol.xm = P.xm; pol.var_new = bvar(P, t); pol.var_prev = bvar(P, t + 1); pol.secmax = P.secmax; pol.secabs = P.secabs;
+    const float* sit = bamp_xmap<BN, KC>(P, AllRows{}, lds, row0, col0, nrows, ncols);
+    const BampDenoisePolicy pol = bamp_policy<BN, KC>(P, t, lds, sit, row0, col0, ncols, 0);
     PartAcc pa;
     if (P.elementwise) {
         // no batch-global shift in random_denoiser: the section statistics stay neutral
@@ -424,13 +235,7 @@ __device__ __forceinline__ void bamp_finish(const BampK& P, int t, uint32_t notc
     nx.fixed = fixed;
     nx.fixed_all = (fixed < 0) ? 1 : 0;
     P.iters[t + 1] = nx;
-    if (nx.stopped || t + 1 == P.max_iter) {
-        amp_status s;
-        s.T = t + 1; s.nan_state = fixed != 0 ? 1 : 0; s.stopped = nx.stopped;
-        s.gemm = P.h2 ? AMP_ARITH_FP16X2 : P.x3 ? AMP_ARITH_BF16X3 : AMP_ARITH_F32;
-        s.last_scalar[0] = s.last_scalar[1] = s.last_scalar[2] = s.last_scalar[3] = 0.f;
-        *P.status = s;
-    }
+    if (nx.stopped || t + 1 == P.max_iter) *P.status = bamp_status(P, t, fixed, nx.stopped);
 }
 
 // Reduction and allclose decision (bamp.py:140).  The rare exact-float64 path (a section's
@@ -455,18 +260,10 @@ __global__ __launch_bounds__(BRWG) void bamp_r(BampK P, Const64 c64, int t) {
         if (threadIdx.x == 0) bamp_finish(P, t, 1u, -1);
     } else if (part_danger(pa)) {
         const double slack = logit_slack(pa.maxabs);
-        const float2* xp2 = reinterpret_cast<const float2*>(P.xmap);
-        const float* cov = P.cov;
-        const int M = P.M;
         double gm = 0.0;
         for (int sct = threadIdx.x; sct < P.B * P.L; sct += blockDim.x) {
             if ((double)P.secabs[sct] < pa.maxabs - slack) continue;
-            const size_t o0 = (size_t)sct * M;
-            auto ld = [=](int m, float& rr, float& ri, float& it) {
-                const float2 v = xp2[o0 + m];
-                rr = v.x; ri = v.y; it = 1.0f / (cov[o0 + m] * 0.5f);
-            };
-            gm = fmax(gm, section_absmax_f64(ld, M, c64));
+            gm = fmax(gm, section_absmax_f64(bamp_section_load(P, (size_t)sct * P.M), P.M, c64));
         }
         gm = group_max(gm, 64);
         if ((threadIdx.x & 63) == 0) s_d[threadIdx.x >> 6] = gm;
@@ -491,45 +288,19 @@ __device__ __forceinline__ int2* bamp_fix_counts(const BampK& P, int t) {
     return reinterpret_cast<int2*>(P.parts + (size_t)t * P.nblk);
 }
 
-__device__ __forceinline__ int bamp_block_sum_int(int v, int* s_i) {
-    v = group_sum(v, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_i[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int tot = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_i[w];
-    return tot;
-}
-
 // the out-of-range sections of a pending record, recomputed with the reference's exact float64
 // op sequence (exact_section_f64): xmmse, var and the allclose delta against the previous var
 __device__ __forceinline__ void bamp_fix_sec_body(const BampK& P, const Const64& c64, int t, const BampIter& pend,
                                                   int* s_i) {
-    const float2* xp2 = reinterpret_cast<const float2*>(P.xmap);
-    float2* x2 = reinterpret_cast<float2*>(P.xm);
-    const float* cov = P.cov;
-    float* vn = bvar(P, t);
-    const float* vp = bvar(P, t + 1);
-    const int M = P.M;
     int cnt = 0, dnc = 0;
     for (int sct = blockIdx.x * blockDim.x + threadIdx.x; sct < P.B * P.L; sct += gridDim.x * blockDim.x) {
         if (!((double)P.secmax[sct] - pend.G < AMP_DANGER + pend.slack)) continue;
-        const size_t o0 = (size_t)sct * M;
-        auto ld = [=](int m, float& rr, float& ri, float& it) {
-            const float2 v = xp2[o0 + m];
-            rr = v.x; ri = v.y; it = 1.0f / (cov[o0 + m] * 0.5f);
-        };
-        auto st = [&](int m, float xr, float xi, float var) {
-            const size_t o = o0 + m;
-            dnc += (torch_close(var, vp[o]) ? 0 : 1) - (torch_close(vn[o], vp[o]) ? 0 : 1);
-            x2[o] = make_float2(xr, xi);
-            vn[o] = var;
-        };
-        exact_section_f64<true>(ld, st, M, c64, pend.G);
+        const size_t o0 = (size_t)sct * P.M;
+        exact_section_f64<true>(bamp_section_load(P, o0), bamp_section_store(P, t, o0, &dnc), P.M, c64, pend.G);
         ++cnt;
     }
-    cnt = bamp_block_sum_int(cnt, s_i);
-    dnc = bamp_block_sum_int(dnc, s_i);
+    cnt = block_sum(cnt, s_i);
+    dnc = block_sum(dnc, s_i);
     if (threadIdx.x == 0) bamp_fix_counts(P, t)[blockIdx.x] = make_int2(cnt, dnc);
 }
 
@@ -543,33 +314,16 @@ __global__ __launch_bounds__(AMP_WG) void bamp_fixall(BampK P, Const64 c64, int 
         const int2* c = bamp_fix_counts(P, t);
         int fixed = 0, dnc = 0;
         for (int i = threadIdx.x; i < (int)gridDim.x; i += blockDim.x) { fixed += c[i].x; dnc += c[i].y; }
-        fixed = bamp_block_sum_int(fixed, s_i);
-        dnc = bamp_block_sum_int(dnc, s_i);
+        fixed = block_sum(fixed, s_i);
+        dnc = block_sum(dnc, s_i);
         if (threadIdx.x == 0) bamp_finish(P, t, (uint32_t)((int)pend.notclose + dnc), fixed);
     }
 }
 
-// Tracker (bamp.py:13-25): xmmse = 0, var(prev) = 1, z = y, u = 0 + sigma2 -> 1/u.
 // ---- trial-sharded iteration (amp_bamp_run_sharded; SURVEY §8(e) exact-compat) ----
 // bamp_r split at its batch-global values, as the VAMP stages (amp_vamp.hip vamp_xr*): the
 // not-close count (bamp.py:140) and max|xi| / min section max (bamp.py:70) after xr1, the rare
 // path's exact max|xi| after xr2 and its recomputed sections' deltas after xr3.
-__device__ inline void bamp_record(const BampK& P, int t, bool stop, int fixed) {
-    BampIter nx{};
-    nx.stopped = stop ? 1 : 0;
-    nx.T = t + 1;
-    nx.fixed = fixed;
-    nx.fixed_all = (fixed < 0) ? 1 : 0;
-    P.iters[t + 1] = nx;
-    if (nx.stopped || t + 1 == P.max_iter) {
-        amp_status s;
-        s.T = t + 1; s.nan_state = fixed != 0 ? 1 : 0; s.stopped = nx.stopped;
-        s.gemm = P.h2 ? AMP_ARITH_FP16X2 : P.x3 ? AMP_ARITH_BF16X3 : AMP_ARITH_F32;
-        s.last_scalar[0] = s.last_scalar[1] = s.last_scalar[2] = s.last_scalar[3] = 0.f;
-        *P.status = s;
-    }
-}
-
 __global__ __launch_bounds__(BRWG) void bamp_xr1(BampK P, int t) {
     __shared__ __attribute__((aligned(16))) float lds[512];
     XState* xs = P.xs;
@@ -605,18 +359,11 @@ __global__ __launch_bounds__(BRWG) void bamp_xr2(BampK P, Const64 c64, int t) {
     }
     PartAcc pa = bamp_xs_global(*xs);
     if (!part_allnan(pa) && part_danger(pa)) {
-        const float2* xp2 = reinterpret_cast<const float2*>(P.xmap);
-        const float* cov = P.cov;
-        const int M = P.M;
         const double G32 = pa.maxabs, slack = logit_slack(G32);
         double gm = 0.0;
         for (int sct = threadIdx.x; sct < P.B * P.L; sct += blockDim.x) {
             if (!((double)P.secabs[sct] >= G32 - slack)) continue;
-            const size_t o0 = (size_t)sct * M;
-            gm = fmax(gm, section_absmax_f64([=](int m, float& rr, float& ri, float& it) {
-                const float2 v = xp2[o0 + m];
-                rr = v.x; ri = v.y; it = 1.0f / (cov[o0 + m] * 0.5f);
-            }, M, c64));
+            gm = fmax(gm, section_absmax_f64(bamp_section_load(P, (size_t)sct * P.M), P.M, c64));
         }
         gm = group_max(gm, 64);
         if ((threadIdx.x & 63) == 0) s_d[threadIdx.x >> 6] = gm;
@@ -636,7 +383,7 @@ __global__ __launch_bounds__(BRWG) void bamp_xr2(BampK P, Const64 c64, int t) {
         fixed = -1;
     }
     if (threadIdx.x == 0) {
-        bamp_record(P, t, pa.notclose == 0, fixed);
+        bamp_finish(P, t, pa.notclose, fixed);
         xs->mode = 0;
         xs->gmax[0] = 0.0;
     }
@@ -651,29 +398,12 @@ __global__ __launch_bounds__(BRWG) void bamp_xr3(BampK P, Const64 c64, int t) {
     }
     const PartAcc pa = bamp_xs_global(*xs);
     const double G = xs->gmax[0], slack = logit_slack(pa.maxabs);
-    float* vn = bvar(P, t);
-    const float* vp = bvar(P, t + 1);
-    const float2* xp2 = reinterpret_cast<const float2*>(P.xmap);
-    const float* cov = P.cov;
-    float2* x2 = reinterpret_cast<float2*>(P.xm);
-    const int M = P.M;
     int dnc = 0, cnt = 0;
     for (int sct = threadIdx.x; sct < P.B * P.L; sct += blockDim.x) {
         if (!((double)P.secmax[sct] - G < AMP_DANGER + slack)) continue;
         ++cnt;
-        const size_t o0 = (size_t)sct * M;
-        exact_section_f64<true>(
-            [=](int m, float& rr, float& ri, float& it) {
-                const float2 v = xp2[o0 + m];
-                rr = v.x; ri = v.y; it = 1.0f / (cov[o0 + m] * 0.5f);
-            },
-            [&](int m, float xr, float xi, float var) {
-                const size_t o = o0 + m;
-                dnc += (torch_close(var, vp[o]) ? 0 : 1) - (torch_close(vn[o], vp[o]) ? 0 : 1);
-                x2[o] = make_float2(xr, xi);
-                vn[o] = var;
-            },
-            M, c64, G);
+        const size_t o0 = (size_t)sct * P.M;
+        exact_section_f64<true>(bamp_section_load(P, o0), bamp_section_store(P, t, o0, &dnc), P.M, c64, G);
     }
     dnc = group_sum(dnc, 64);
     cnt = group_sum(cnt, 64);
@@ -691,27 +421,12 @@ __global__ void bamp_xr4(BampK P, int t) {
     if (xs->mode != 2 || threadIdx.x != 0) return;
     const PartAcc pa = bamp_xs_global(*xs);
     const long long nc = (long long)pa.notclose + (long long)xs->fix[1];
-    bamp_record(P, t, nc == 0, (int)xs->fix[2]);
+    bamp_finish(P, t, nc == 0 ? 0u : 1u, (int)xs->fix[2]);
 }
 
+// Tracker (bamp.py:13-25) and the record of iteration 0
 __global__ void bamp_init_kernel(BampK P) {
-    const size_t BN_ = (size_t)P.B * P.N, Bn = (size_t)P.B * P.n;
-    const size_t tot = BN_ > Bn ? BN_ : Bn;
-    const float iu = 1.0f / P.sigma2;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < tot; e += (size_t)gridDim.x * blockDim.x) {
-        if (e < BN_) {
-            reinterpret_cast<float2*>(P.xm)[e] = make_float2(0.f, 0.f);
-            P.var1[e] = 1.0f;
-        }
-        if (e < Bn) {
-            reinterpret_cast<float2*>(P.z)[e] = reinterpret_cast<const float2*>(P.y)[e];
-            P.invu[P.ild == P.n ? e : (e / P.n) * P.ild + e % P.n] = iu;
-        }
-        if (e < (size_t)P.B) {   // the pads of the invu and s rows (bamp_ild / bamp_sld), zeroed once
-            for (int k = P.n; k < P.ild; ++k) P.invu[e * P.ild + k] = 0.f;
-            for (int k = 2 * P.n; k < P.sld; ++k) P.s[e * P.sld + k] = 0.f;
-        }
-    }
+    bamp_init_state(P);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         P.rcnt[0] = 0u; P.rcnt[1] = 0u;
         BampIter it{};
@@ -790,14 +505,7 @@ static void launch_kb2_kk(const BampK& P, const Const64& c64, int gr, int t, hip
 }
 
 static void launch_kb2(const BampK& P, const Const64& c64, int gr, int t, hipStream_t st) {
-    switch (P.c.K) {
-    case 1: launch_kb2_kk<1>(P, c64, gr, t, st); break;
-    case 2: launch_kb2_kk<2>(P, c64, gr, t, st); break;
-    case 4: launch_kb2_kk<4>(P, c64, gr, t, st); break;
-    case 8: launch_kb2_kk<8>(P, c64, gr, t, st); break;
-    case 16: launch_kb2_kk<16>(P, c64, gr, t, st); break;
-    default: launch_kb2_kk<64>(P, c64, gr, t, st); break;
-    }
+    dispatch_K(P.c.K, [&](auto kk) { launch_kb2_kk<decltype(kk)::value>(P, c64, gr, t, st); });
 }
 
 static std::once_flag g_bamp_once;
@@ -855,7 +563,7 @@ static int bamp_setup(const amp_dims* d, const amp_constellation* c, const amp_b
     AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_bamp_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
     rc = bamp_attrs();
     if (rc) return rc;
-    bamp_geometry(d, P);
+    bamp_geometry(d, d->B, P);
     P.max_iter = a->max_iter;
     P.sigma2 = (float)a->noise_var;
     P.Wabs2 = w.Wabs2; P.WH = w.WH; P.Wabs2T = w.Wabs2T; P.WHH = w.WHH;
@@ -921,12 +629,8 @@ static int bamp_prepare_impl(const BampK& P, const amp_bamp_args* a, hipStream_t
         j[2] = CWeightJob{H, 1, P.N, 0, nullptr, P.N, P.n, (float*)P.Wabs2T, P.n, P.N, WPACKH2_ABS2, BH2_EX};
         j[3] = CWeightJob{H, 1, P.N, 1, nullptr, P.N, P.n, (float*)P.WHH, P.n, P.N, WPACKH2, BH2_EX};
         if ((rc = build_cweights(j, 4, nullptr, 0, st))) return rc;
-    } else {
-    // weights, once per forward (Tracker: adj, abs2, abs2T, bamp.py:17-19)
-    if ((rc = build_abs2_weight(H, P.N, 1, P.n, P.N, (float*)P.Wabs2, P.kapA1, P.ncpA1, st))) return rc;
-    if ((rc = build_cweight(H, P.N, 1, 0, nullptr, P.n, P.N, (float*)P.WH, P.kapA2, P.ncpA2, st))) return rc;
-    if ((rc = build_abs2_weight(H, 1, P.N, P.N, P.n, (float*)P.Wabs2T, P.kapB1, P.ncpB1, st))) return rc;
-    if ((rc = build_cweight(H, 1, P.N, 1, nullptr, P.N, P.n, (float*)P.WHH, P.kapB2, P.ncpB2, st))) return rc;
+    } else if ((rc = bamp_pack_f32(P, H, st))) {   // the f32 weights and their band ranges, once per forward
+        return rc;
     }
     if (P.band[0] && (P.h2 || P.x3)) {
         // per column tile: real |H|^2 (fp16x2 two planes, bf16x3 three; 8 16-tiles per 128
@@ -936,12 +640,6 @@ static int bamp_prepare_impl(const BampK& P, const amp_bamp_args* a, hipStream_t
         if ((rc = h2_kband(P.WH, pc, P.N / 32, 4, P.ncpA2 / 128, P.n / 16, const_cast<int*>(P.band[1]), st))) return rc;
         if ((rc = h2_kband(P.Wabs2T, pr, P.n / 32, 8, P.ncpB1 / 128, P.N / 16, const_cast<int*>(P.band[2]), st))) return rc;
         if ((rc = h2_kband(P.WHH, pc, P.n / 32, P.bn / 32, P.ncpB2 / P.bn, P.N / 16, const_cast<int*>(P.band[3]), st))) return rc;
-    } else if (P.band[0]) {
-        const float* wts[4] = {P.Wabs2, P.WH, P.Wabs2T, P.WHH};
-        const int kaps[4] = {P.kapA1, P.kapA2, P.kapB1, P.kapB2}, ncps[4] = {P.ncpA1, P.ncpA2, P.ncpB1, P.ncpB2};
-        const int bns[4] = {128, 128, 128, P.bn};
-        for (int i = 0; i < 4; ++i)
-            if ((rc = weight_kband(wts[i], kaps[i], ncps[i], bns[i], const_cast<int*>(P.band[i]), st))) return rc;
     }
     const size_t tot = std::max((size_t)P.B * P.N, (size_t)P.B * P.n);
     const int g = (int)std::min<size_t>((tot + 255) / 256, 2048);

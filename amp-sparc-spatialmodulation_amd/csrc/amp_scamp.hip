@@ -18,254 +18,72 @@
 
 namespace amp {
 
-// z = y - A xmmse + b z ; phi = sigma2 + gamma ; s = z / phi   (scamp.py:45-51, 57)
-// X3: the bf16x3 tile (amp_gemm_x3.h) in an instantiation of its own, so the f32 tiles keep their
-// register budget (one instantiation holding both ran the f32 ISI shape 25 % slower)
+// The epilogues are amp_scamp.h's, shared with the independent-trial engine
+// (amp_scamp_trials.hip): a GEMM kernel here is its entry guard, the tile of its arithmetic and the
+// epilogue calls under the AllRows guard.
+
+// scamp_residual.  X3: the bf16x3 tile (amp_gemm_x3.h) in an instantiation of its own, so the f32
+// tiles keep their register budget (one instantiation holding both ran the f32 ISI shape 25 % slower)
 template <int KC, bool X3 = false>
 __global__ __launch_bounds__(AMP_WG) void scamp_ka(ScampK P, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (P.iters[t].stopped) return;
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
-    const int twoN = 2 * P.N, twon = 2 * P.n, sld = scamp_sld(P.n);
+    const int twoN = 2 * P.N;
     const int kb = P.bandA ? P.bandA[2 * tile.cb] : 0, ke = P.bandA ? P.bandA[2 * tile.cb + 1] : -1;
     if constexpr (X3)
         gemm_tile_x3<128, true>(P.lap, P.rows_pad, P.N, P.WA, row0, col0, lds, kb, ke);
     else
         gemm_tile<128, ALoadPlain, KC>(ALoadPlain{P.xm, twoN, P.B, twoN}, P.WA, P.kapA, row0, col0, lds, kb, ke);
-    using C = GemmCfg<128, KC>;
-    const float* psi = spsi(P, t + 1);               // psi of iteration t-1 (ones at t = 0)
-    const float* phi_old = sphi(P, t + 1);           // +inf at t = 0 (scamp.py:19)
-    float* phi_new = sphi(P, t);
-    // gamma of each (trial, output block) the tile touches, formed once (the same float32 sum as
-    // scamp_gamma) instead of once per element: Lin MACs of global loads per element had made the
-    // epilogue, not the GEMM, the cost of a Lin > 1 tile
-    // The rows' psi and the W rows come into LDS first (coalesced), so the serial float32 sums
-    // read LDS, not a chain of dependent global loads.
-    const int lo0 = (col0 >> 1) / P.Nr, nlo = (min((col0 >> 1) + 63, P.n - 1)) / P.Nr - lo0 + 1;
-    const int Lin = P.Lin;
-    float* sg = lds + C::CTILE_FLOATS;                 // [GBM][nlo] gamma
-    float* sp = sg + GBM * nlo;                        // [GBM][Lin] psi rows
-    float* sw = sp + GBM * Lin;                        // [nlo][Lin] W rows lo0 ..
-    const bool per_block = C::CTILE_FLOATS + GBM * nlo + GBM * Lin + nlo * Lin <= C::A_FLOATS;
-    if (per_block) {
-        for (int e = threadIdx.x; e < GBM * Lin; e += AMP_WG) {
-            const int row = row0 + e / Lin;
-            sp[e] = row < P.B ? psi[(size_t)row0 * Lin + e] : 0.f;
-        }
-        for (int e = threadIdx.x; e < nlo * Lin; e += AMP_WG) sw[e] = P.W[(size_t)lo0 * Lin + e];
-        __syncthreads();
-        for (int e = threadIdx.x; e < GBM * nlo; e += AMP_WG) {
-            const int rho = e / nlo, j = e - rho * nlo;
-            float g = 0.f;                             // scamp_gamma's sum, in its order
-            for (int lc = 0; lc < Lin; ++lc) g += sw[j * Lin + lc] * sp[rho * Lin + lc];
-            sg[e] = g / (float)Lin;
-        }
-        __syncthreads();
-    }
-    // Every global load of this thread's elements is issued before any store: the stores to z / s
-    // may alias the next element's loads as far as the compiler knows, and a load-compute-store loop
-    // waited a full memory latency per element (each element reads and writes only its own z).
-    constexpr int IT = GBM * 64 / AMP_WG;
-    float2 yv[IT], zv[IT];
-    float po[IT];
-#pragma unroll
-    for (int u = 0; u < IT; ++u) {
-        // unconditional loads at a clamped index (a lane-divergent branch around them serialises
-        // their latencies, amp_gemm.h ALoadPlain); out-of-range elements are never stored
-        const int e = threadIdx.x + u * AMP_WG;
-        const int rho = e >> 6, cp = e & 63;
-        const int row = min(row0 + rho, P.B - 1), i = min((col0 >> 1) + cp, P.n - 1);
-        const size_t oc = (size_t)row * twon + 2 * i;
-        yv[u] = *reinterpret_cast<const float2*>(P.y + oc);
-        zv[u] = *reinterpret_cast<const float2*>(P.z + oc);
-        po[u] = phi_old[(size_t)row * P.Lout + i / P.Nr];
-    }
-#pragma unroll
-    for (int u = 0; u < IT; ++u) {
-        const int e = threadIdx.x + u * AMP_WG;
-        const int rho = e >> 6, cp = e & 63;
-        const int row = row0 + rho, i = (col0 >> 1) + cp;
-        if (row < P.B && i < P.n) {
-            const int lo = i / P.Nr;
-            const float gma = per_block ? sg[rho * nlo + lo - lo0] : scamp_gamma(P, psi + (size_t)row * P.Lin, lo);
-            const float b = gma / po[u];
-            const size_t oc = (size_t)row * twon + 2 * i;
-            const float ar = lds[rho * C::LDC + 2 * cp], ai = lds[rho * C::LDC + 2 * cp + 1];
-            const float zr = (yv[u].x - ar) + b * zv[u].x;
-            const float zi = (yv[u].y - ai) + b * zv[u].y;
-            const float ph = P.sigma2 + gma;
-            const float iph = 1.0f / ph;
-            *reinterpret_cast<float2*>(P.z + oc) = make_float2(zr, zi);
-            *reinterpret_cast<float2*>(P.s + (size_t)row * sld + 2 * i) = make_float2(zr * iph, zi * iph);
-            if (i % P.Nr == 0) phi_new[(size_t)row * P.Lout + lo] = ph;
-        }
-    }
+    scamp_residual<KC>(P, AllRows{}, t, lds, row0, col0);
 }
 
-struct ScampDenoisePolicy {
-    const float* tile;
-    const float* tau_tile;   // LDS [32][Lin] tau of the tile's rows and blocks lc0 .. lc0 + Lin - 1
-    int ldc, spr, M, N, Nt, L, row0, colc0, Lin, lc0;
-    float* xm;
-    float* secmax;
-    float* secabs;
-    __device__ __forceinline__ void load(int sec, int m, float& rr, float& ri, float& it) const {
-        const int rho = sec / spr, sj = sec - rho * spr;
-        const int cc = sj * M + m;
-        const float2 v = *reinterpret_cast<const float2*>(tile + rho * ldc + 2 * cc);
-        rr = v.x; ri = v.y;
-        it = 1.0f / (tau_tile[rho * Lin + (colc0 + cc) / Nt - lc0] * 0.5f);   // tau_use / 2 (scamp.py:63)
-    }
-    __device__ __forceinline__ void store(int sec, int m, float xr, float xi, float, PartAcc&) const {
-        const int rho = sec / spr, sj = sec - rho * spr;
-        const size_t o = (size_t)(row0 + rho) * N + colc0 + sj * M + m;
-        *reinterpret_cast<float2*>(xm + 2 * o) = make_float2(xr, xi);
-    }
-    __device__ __forceinline__ void section(int sec, float smax, float sabs) const {
-        const int rho = sec / spr, sj = sec - rho * spr;
-        const size_t o = (size_t)(row0 + rho) * L + (colc0 / M) + sj;
-        secmax[o] = smax;
-        secabs[o] = sabs;
-    }
-};
-
-// tau = L / (W^T (1/phi)) / Mr ; xmap = xmmse + tau (A^H s) ; xmmse = denoiser ; psi   (scamp.py:53-59)
+// scamp_xmap ; xmmse = denoiser ; psi where the tile holds whole coupling blocks   (scamp.py:53-59)
 template <int BN, int KK, int KC = GKC, bool X3 = false>
 __global__ __launch_bounds__(AMP_WG) void scamp_kb(ScampK P, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (P.iters[t].stopped) return;
-    using C = GemmCfg<BN, KC>;
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    const int twoN = 2 * P.N, sld = scamp_sld(P.n);
+    const int sld = scamp_sld(P.n);
     const int kb = P.bandB ? P.bandB[2 * tile.cb] : 0, ke = P.bandB ? P.bandB[2 * tile.cb + 1] : -1;
     if constexpr (X3)
         gemm_tile_x3<BN, true>(P.lap, P.rows_pad, P.n, P.WAH, row0, col0, lds, kb, ke);
     else
         gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, sld, P.B, sld}, P.WAH, P.kapB, row0, col0, lds, kb, ke);
-    const int nrows = min(GBM, P.B - row0), ncols = min(BN, twoN - col0);
-    const int lc0 = (col0 / 2) / P.Nt, nlc = max(1, (ncols / 2) / P.Nt);   // coupling blocks in this tile
-    // tau of the blocks this tile covers only (blocks lc0 .. lc0 + ntc - 1): each is written to
-    // P.tau by the tile that holds its first column
-    const int ntc = (col0 / 2 + ncols / 2 - 1) / P.Nt - lc0 + 1;
-    float* tau_t = lds + C::CTILE_FLOATS;                                    // [32][ntc]
-    const float* phi = sphi(P, t);
-    // the rows' 1 / phi and the W columns lc0 .. into LDS first (coalesced): the serial float32
-    // sums then read LDS instead of a chain of dependent global loads
-    const int Lout = P.Lout;
-    float* siph = tau_t + GBM * ntc;                                         // [32][Lout] 1 / phi
-    float* swc = siph + GBM * Lout;                                          // [ntc][Lout] W columns
-    const bool staged = C::CTILE_FLOATS + GBM * ntc + GBM * Lout + ntc * Lout <= C::A_FLOATS;
-    if (staged) {
-        for (int e = threadIdx.x; e < GBM * Lout; e += AMP_WG)
-            siph[e] = e / Lout < nrows ? 1.0f / phi[(size_t)row0 * Lout + e] : 0.f;
-        for (int e = threadIdx.x; e < ntc * Lout; e += AMP_WG) {
-            const int j = e / Lout, lo = e - j * Lout;
-            swc[e] = P.W[lo * P.Lin + lc0 + j];
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < GBM * ntc; e += AMP_WG) {
-        const int rho = e / ntc, lc = lc0 + e - rho * ntc;
-        float tv = 0.f;
-        if (rho < nrows) {
-            float acc = 0.f;   // (W^T (1/phi))[lc] in float32
-            if (staged)
-                for (int lo = 0; lo < Lout; ++lo) acc += swc[(lc - lc0) * Lout + lo] * siph[rho * Lout + lo];
-            else
-                for (int lo = 0; lo < P.Lout; ++lo)
-                    acc += P.W[lo * P.Lin + lc] * (1.0f / phi[(size_t)(row0 + rho) * P.Lout + lo]);
-            tv = ((1.0f / acc) * (float)P.L) / (float)P.Nr;          // L / x = recip(x) * L ; / Mr
-            if (lc * P.Nt >= col0 / 2) P.tau[(size_t)(row0 + rho) * P.Lin + lc] = tv;
-        }
-        tau_t[e] = tv;
-    }
-    __syncthreads();
-    {
-        // xmmse of every element of this thread first (the xmap stores may alias them as far as
-        // the compiler knows: one load latency per element otherwise)
-        constexpr int IT = GBM * BN / AMP_WG;
-        float xv[IT];
-#pragma unroll
-        for (int u = 0; u < IT; ++u) {
-            // unconditional loads at a clamped index (see scamp_ka); out-of-range elements unused
-            const int e = threadIdx.x + u * AMP_WG, rho = min(e / BN, nrows - 1), cc = min(e % BN, ncols - 1);
-            xv[u] = P.xm[(size_t)(row0 + rho) * twoN + col0 + cc];
-        }
-#pragma unroll
-        for (int u = 0; u < IT; ++u) {
-            const int e = threadIdx.x + u * AMP_WG, rho = e / BN, cc = e % BN;
-            if (rho < nrows && cc < ncols) {
-                const size_t o = (size_t)(row0 + rho) * twoN + col0 + cc;
-                const float tv = tau_t[rho * ntc + ((col0 + cc) >> 1) / P.Nt - lc0];
-                const float xp = xv[u] + tv * lds[rho * C::LDC + cc];
-                P.xmap[o] = xp;
-                lds[rho * C::LDC + cc] = xp;
-            }
-        }
-    }
-    __syncthreads();
-    ScampDenoisePolicy pol;
-    pol.tile = lds; pol.tau_tile = tau_t; pol.ldc = C::LDC; pol.M = P.M; pol.N = P.N; pol.Nt = P.Nt; pol.L = P.L;
-    pol.spr = (ncols / 2) / P.M; pol.row0 = row0; pol.colc0 = col0 / 2; pol.Lin = ntc; pol.lc0 = lc0;
-    pol.xm = P.xm; pol.secmax = P.secmax; pol.secabs = P.secabs;
+    const int nrows = min(GBM, P.B - row0), ncols = min(BN, 2 * P.N - col0);
+    const ScampTileBlocks tb = scamp_tile_blocks(P, col0, ncols);
+    const float* tau_t = scamp_xmap<BN, KC>(P, AllRows{}, t, lds, row0, col0, nrows, ncols, tb);
+    const ScampDenoisePolicy pol = scamp_policy<BN, KC>(P, lds, tau_t, row0, col0, ncols, tb, 0);
     PartAcc pa;
     denoise_sections<false, KK>(pol, nrows * pol.spr, P.M, P.c, pa);
     __syncthreads();
-    // psi = 1 - sum_block |xmmse|^2 / Na (scamp.py:59) from the freshly written tile
-    const float* psi_prev = spsi(P, t + 1);
-    float* psi_new = spsi(P, t);
+    // psi from the freshly written tile: one thread per (row, whole coupling block)
     unsigned nc = 0;
-    for (int e = threadIdx.x; e < (P.psi_split ? 0 : GBM * nlc); e += AMP_WG) {
-        const int rho = e / nlc, b = e % nlc;
-        if (rho >= nrows) continue;
-        const int lc = lc0 + b;
-        const float2* xr = reinterpret_cast<const float2*>(P.xm) + (size_t)(row0 + rho) * P.N + (size_t)lc * P.Nt;
-        double ssum = 0.0;
-        for (int m = 0; m < P.Nt; ++m) {
-            const float2 v = xr[m];
-            const float a = (float)sqrt((double)v.x * v.x + (double)v.y * v.y);   // torch abs (hypot)
-            ssum += (double)(a * a);
-        }
-        const float ps = 1.0f - (float)ssum / (float)P.Na;
-        const size_t o = (size_t)(row0 + rho) * P.Lin + lc;
-        nc += torch_close(ps, psi_prev[o]) ? 0u : 1u;                // scamp.py:105
-        psi_new[o] = ps;
+    for (int e = threadIdx.x; e < (P.psi_split ? 0 : GBM * tb.nlc); e += AMP_WG) {
+        const int rho = e / tb.nlc, b = e % tb.nlc;
+        if (rho < nrows) nc += scamp_psi_in_tile(P, t, row0 + rho, tb.lc0 + b);
     }
     pa.notclose += nc;
     part_block_store(pa, P.parts + (size_t)t * P.nblk + blockIdx.y * gridDim.x + blockIdx.x, lds);
 }
 
 // psi (scamp.py:59) and its allclose count (scamp.py:105) when the A^H tile holds only part of
-// a coupling block: one thread per (trial, block), after every tile of the iteration is written.
-__device__ __forceinline__ unsigned block_sum_u32(unsigned v, unsigned* s_u) {
-    v = group_sum(v, 64);
-    if ((threadIdx.x & 63) == 0) s_u[threadIdx.x >> 6] = v;
-    __syncthreads();
-    unsigned tot = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_u[w];
-    return tot;
-}
+// a coupling block, after every tile of the iteration is written.
 
 __global__ __launch_bounds__(AMP_WG) void scamp_psi(ScampK P, int t) {
     // one wavefront per (trial, coupling block): lanes stride the block's Nt entries
     __shared__ unsigned s_u[AMP_WG / 64];
     if (P.iters[t].stopped) return;
-    const float* psi_prev = spsi(P, t + 1);
-    float* psi_new = spsi(P, t);
     const int lane = threadIdx.x & 63;
     const int nwave = gridDim.x * (AMP_WG / 64);
     unsigned nc = 0;
     for (int blk = blockIdx.x * (AMP_WG / 64) + (threadIdx.x >> 6); blk < P.B * P.Lin; blk += nwave) {
         const double ssum = scamp_block_energy(reinterpret_cast<const float2*>(P.xm) + (size_t)blk * P.Nt, P.Nt);
-        if (lane == 0) {
-            const float ps = 1.0f - (float)ssum / (float)P.Na;
-            nc += torch_close(ps, psi_prev[blk]) ? 0u : 1u;
-            psi_new[blk] = ps;
-        }
+        if (lane == 0) nc += (unsigned)scamp_psi_store(P, t, blk, ssum);
     }
-    nc = block_sum_u32(nc, s_u);
+    nc = block_sum(nc, s_u);
     if (threadIdx.x == 0) P.psi_nc[(size_t)t * P.psi_nblk + blockIdx.x] = nc;
 }
 
@@ -278,20 +96,7 @@ __global__ __launch_bounds__(AMP_WG) void scamp_psi(ScampK P, int t) {
 // scamp_fix_sec / scamp_fix_psi and settle the counts across ranks.  (Before: one
 // workgroup recomputed every such section, 267 us per iteration at cfg3's NaN onset.)
 __device__ __forceinline__ void scamp_finish(const ScampK& P, int t, uint32_t notclose, int fixed, int fixed_all) {
-    ScampIter nx;
-    nx.stopped = notclose == 0 ? 1 : 0;
-    nx.T = t + 1;
-    nx.fixed = fixed;
-    nx.fixed_all = fixed_all;
-    nx.G = 0.0; nx.slack = 0.0; nx.notclose = notclose; nx.active = 0; nx.pad[0] = nx.pad[1] = 0;
-    P.iters[t + 1] = nx;
-    if (nx.stopped || t + 1 == P.max_iter) {
-        amp_status s;
-        s.T = t + 1; s.nan_state = fixed != 0 ? 1 : 0; s.stopped = nx.stopped;
-        s.gemm = P.lx3 ? AMP_ARITH_BF16X3 : AMP_ARITH_F32;
-        s.last_scalar[0] = s.last_scalar[1] = s.last_scalar[2] = s.last_scalar[3] = 0.f;
-        *P.status = s;
-    }
+    scamp_record(P, &P.iters[t + 1], P.status, t, notclose, fixed, fixed_all);
 }
 
 __global__ __launch_bounds__(SRWG) void scamp_r(ScampK P, Const64 c64, int t) {
@@ -307,7 +112,7 @@ __global__ __launch_bounds__(SRWG) void scamp_r(ScampK P, Const64 c64, int t) {
         __shared__ unsigned s_u[SRWG / 64];
         unsigned nc = 0;
         for (int i = threadIdx.x; i < P.psi_nblk; i += blockDim.x) nc += P.psi_nc[(size_t)t * P.psi_nblk + i];
-        pa.notclose += block_sum_u32(nc, s_u);
+        pa.notclose += block_sum(nc, s_u);
     }
     if (part_allnan(pa)) {
         if (!cur.fixed_all) {
@@ -320,20 +125,10 @@ __global__ __launch_bounds__(SRWG) void scamp_r(ScampK P, Const64 c64, int t) {
         // exact float64 batch max |xi| over the candidate sections (those within the float32
         // estimate's slack of the float32 batch max)
         const double slack = logit_slack(pa.maxabs);
-        const float2* xp2 = reinterpret_cast<const float2*>(P.xmap);
-        const float* tau = P.tau;
-        const int M = P.M, L = P.L, N = P.N, Nt = P.Nt, Lin = P.Lin;
         double gm = 0.0;
-        for (int sct = threadIdx.x; sct < P.B * L; sct += blockDim.x) {
+        for (int sct = threadIdx.x; sct < P.B * P.L; sct += blockDim.x) {
             if ((double)P.secabs[sct] < pa.maxabs - slack) continue;
-            const size_t o0 = (size_t)sct * M;
-            const int b = sct / L, lc = (int)((o0 % (size_t)N) / Nt);
-            const float tv = tau[(size_t)b * Lin + lc];
-            auto ld = [=](int m, float& rr, float& ri, float& it) {
-                const float2 v = xp2[o0 + m];
-                rr = v.x; ri = v.y; it = 1.0f / (tv * 0.5f);
-            };
-            gm = fmax(gm, section_absmax_f64(ld, M, c64));
+            gm = fmax(gm, section_absmax_f64(scamp_section_load(P, (size_t)sct * P.M), P.M, c64));
         }
         gm = group_max(gm, 64);
         if ((threadIdx.x & 63) == 0) s_d[threadIdx.x >> 6] = gm;
@@ -341,10 +136,7 @@ __global__ __launch_bounds__(SRWG) void scamp_r(ScampK P, Const64 c64, int t) {
         if (threadIdx.x == 0) {
             double G = 0.0;
             for (int w = 0; w < SRWG / 64; ++w) G = fmax(G, s_d[w]);
-            ScampIter nx;
-            nx.stopped = 0; nx.T = t + 1; nx.fixed = 0; nx.fixed_all = 0;
-            nx.G = G; nx.slack = slack; nx.notclose = pa.notclose; nx.active = 1; nx.pad[0] = nx.pad[1] = 0;
-            P.iters[t + 1] = nx;
+            P.iters[t + 1] = scamp_pending(t, G, slack, pa.notclose);
         }
     } else if (threadIdx.x == 0) {
         scamp_finish(P, t, pa.notclose, 0, 0);
@@ -357,76 +149,33 @@ __device__ __forceinline__ int2* scamp_fix_counts(const ScampK& P, int t) {
     return reinterpret_cast<int2*>(P.parts + (size_t)t * P.nblk);
 }
 
-__device__ __forceinline__ int block_sum_int(int v, int* s_i) {
-    v = group_sum(v, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_i[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int tot = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_i[w];
-    return tot;
-}
-
 __global__ __launch_bounds__(AMP_WG) void scamp_fix_sec(ScampK P, Const64 c64, int t) {
     __shared__ int s_i[AMP_WG / 64];
     const ScampIter pend = P.iters[t + 1];
     if (!pend.active || P.iters[t].stopped) return;
-    const float2* xp2 = reinterpret_cast<const float2*>(P.xmap);
-    float2* x2 = reinterpret_cast<float2*>(P.xm);
-    const int M = P.M, L = P.L, N = P.N, Nt = P.Nt, Lin = P.Lin;
     int cnt = 0;
-    for (int sct = blockIdx.x * blockDim.x + threadIdx.x; sct < P.B * L; sct += gridDim.x * blockDim.x) {
+    for (int sct = blockIdx.x * blockDim.x + threadIdx.x; sct < P.B * P.L; sct += gridDim.x * blockDim.x) {
         if (!((double)P.secmax[sct] - pend.G < AMP_DANGER + pend.slack)) continue;
-        const size_t o0 = (size_t)sct * M;
-        const int b = sct / L, lc = (int)((o0 % (size_t)N) / Nt);
-        const float tv = P.tau[(size_t)b * Lin + lc];
-        auto ld = [=](int m, float& rr, float& ri, float& it) {
-            const float2 v = xp2[o0 + m];
-            rr = v.x; ri = v.y; it = 1.0f / (tv * 0.5f);
-        };
-        auto st = [=](int m, float xr, float xi, float) { x2[o0 + m] = make_float2(xr, xi); };
-        exact_section_f64<false>(ld, st, M, c64, pend.G);
+        const size_t o0 = (size_t)sct * P.M;
+        exact_section_f64<false>(scamp_section_load(P, o0), scamp_section_store(P, o0), P.M, c64, pend.G);
         ++cnt;
     }
-    cnt = block_sum_int(cnt, s_i);
+    cnt = block_sum(cnt, s_i);
     if (threadIdx.x == 0) scamp_fix_counts(P, t)[blockIdx.x].x = cnt;
 }
 
 __device__ __forceinline__ void scamp_fix_psi_body(const ScampK& P, int t, const ScampIter& pend, int* s_i) {
-    const float* psi_prev = spsi(P, t + 1);
-    float* psi_new = spsi(P, t);
-    const int spb = P.Nt / P.M;   // sections per coupling block
     int dnc = 0;
     if (P.Nt > SFIX_SERIAL_NT) {
         // wide blocks: one wavefront per block, in scamp_psi's summation order
         const int nwave = gridDim.x * (blockDim.x >> 6);
-        for (int blk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); blk < P.B * P.Lin; blk += nwave) {
-            if (!scamp_block_hit_wave(P.secmax + (size_t)blk * spb, spb, pend.G, pend.slack)) continue;
-            const float2* xr = reinterpret_cast<const float2*>(P.xm) + (size_t)blk * P.Nt;
-            const double ssum = scamp_block_energy(xr, P.Nt);
-            if ((threadIdx.x & 63) == 0) {
-                const float ps = 1.0f - (float)ssum / (float)P.Na;
-                dnc += (torch_close(ps, psi_prev[blk]) ? 0 : 1) - (torch_close(psi_new[blk], psi_prev[blk]) ? 0 : 1);
-                psi_new[blk] = ps;
-            }
-        }
-    } else
-    for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < P.B * P.Lin; blk += gridDim.x * blockDim.x) {
-        bool hit = false;
-        for (int j = 0; j < spb && !hit; ++j)
-            hit = (double)P.secmax[(size_t)blk * spb + j] - pend.G < AMP_DANGER + pend.slack;
-        if (!hit) continue;
-        const float2* xr = reinterpret_cast<const float2*>(P.xm) + (size_t)blk * P.Nt;
-        double ssum = 0.0;
-        for (int m = 0; m < P.Nt; ++m) {
-            const float a = (float)sqrt((double)xr[m].x * xr[m].x + (double)xr[m].y * xr[m].y);
-            ssum += (double)(a * a);
-        }
-        const float ps = 1.0f - (float)ssum / (float)P.Na;
-        dnc += (torch_close(ps, psi_prev[blk]) ? 0 : 1) - (torch_close(psi_new[blk], psi_prev[blk]) ? 0 : 1);
-        psi_new[blk] = ps;
+        for (int blk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); blk < P.B * P.Lin; blk += nwave)
+            dnc += scamp_fix_psi_wave(P, t, blk, pend);
+    } else {
+        for (int blk = blockIdx.x * blockDim.x + threadIdx.x; blk < P.B * P.Lin; blk += gridDim.x * blockDim.x)
+            dnc += scamp_fix_psi_serial(P, t, blk, pend);
     }
-    dnc = block_sum_int(dnc, s_i);
+    dnc = block_sum(dnc, s_i);
     if (threadIdx.x == 0) scamp_fix_counts(P, t)[blockIdx.x].y = dnc;
 }
 
@@ -449,8 +198,8 @@ __global__ __launch_bounds__(AMP_WG) void scamp_fix_psi_fin(ScampK P, int t) {
         const int2* c = scamp_fix_counts(P, t);
         int fixed = 0, d = 0;
         for (int i = threadIdx.x; i < (int)gridDim.x; i += blockDim.x) { fixed += c[i].x; d += c[i].y; }
-        fixed = block_sum_int(fixed, s_i);
-        d = block_sum_int(d, s_i);
+        fixed = block_sum(fixed, s_i);
+        d = block_sum(d, s_i);
         if (threadIdx.x == 0) scamp_finish(P, t, (uint32_t)((int)pend.notclose + d), fixed, 0);
     }
 }
@@ -472,7 +221,7 @@ __global__ __launch_bounds__(SRWG) void scamp_sxr1(ScampK P, int t) {
     if (P.psi_split) {
         unsigned nc = 0;
         for (int i = threadIdx.x; i < P.psi_nblk; i += blockDim.x) nc += P.psi_nc[(size_t)t * P.psi_nblk + i];
-        pa.notclose += block_sum_u32(nc, s_u);
+        pa.notclose += block_sum(nc, s_u);
     }
     if (threadIdx.x == 0) {
         xs->sum[0] = 0.0;
@@ -504,19 +253,10 @@ __global__ __launch_bounds__(SRWG) void scamp_sxr2(ScampK P, Const64 c64, int t)
     } else if (part_danger(pa)) {
         // this rank's exact float64 max |xi| over its candidate sections (scamp_r's first stage)
         const double slack = logit_slack(pa.maxabs);
-        const float2* xp2 = reinterpret_cast<const float2*>(P.xmap);
-        const float* tau = P.tau;
-        const int M = P.M, L = P.L, N = P.N, Nt = P.Nt, Lin = P.Lin;
         double gm = 0.0;
-        for (int sct = threadIdx.x; sct < P.B * L; sct += blockDim.x) {
+        for (int sct = threadIdx.x; sct < P.B * P.L; sct += blockDim.x) {
             if ((double)P.secabs[sct] < pa.maxabs - slack) continue;
-            const size_t o0 = (size_t)sct * M;
-            const int b = sct / L, lc = (int)((o0 % (size_t)N) / Nt);
-            const float tv = tau[(size_t)b * Lin + lc];
-            gm = fmax(gm, section_absmax_f64([=](int m, float& rr, float& ri, float& it) {
-                const float2 v = xp2[o0 + m];
-                rr = v.x; ri = v.y; it = 1.0f / (tv * 0.5f);
-            }, M, c64));
+            gm = fmax(gm, section_absmax_f64(scamp_section_load(P, (size_t)sct * P.M), P.M, c64));
         }
         gm = group_max(gm, 64);
         if ((threadIdx.x & 63) == 0) s_d[threadIdx.x >> 6] = gm;
@@ -526,10 +266,7 @@ __global__ __launch_bounds__(SRWG) void scamp_sxr2(ScampK P, Const64 c64, int t)
             for (int w = 0; w < SRWG / 64; ++w) G = fmax(G, s_d[w]);
             xs->gmax[0] = G;
             xs->mode = 2;
-            ScampIter nx;   // pending record: G is set to the global value by scamp_sxr3
-            nx.stopped = 0; nx.T = t + 1; nx.fixed = 0; nx.fixed_all = 0;
-            nx.G = G; nx.slack = slack; nx.notclose = pa.notclose; nx.active = 1; nx.pad[0] = nx.pad[1] = 0;
-            P.iters[t + 1] = nx;
+            P.iters[t + 1] = scamp_pending(t, G, slack, pa.notclose);   // G: set to the global value by scamp_sxr3
         }
     } else if (threadIdx.x == 0) {
         scamp_finish(P, t, pa.notclose, 0, 0);
@@ -552,8 +289,8 @@ __global__ __launch_bounds__(AMP_WG) void scamp_sxr4(ScampK P, int t, int nfix) 
     const int2* c = scamp_fix_counts(P, t);
     int fixed = 0, dnc = 0;
     for (int i = threadIdx.x; i < nfix; i += blockDim.x) { fixed += c[i].x; dnc += c[i].y; }
-    fixed = block_sum_int(fixed, s_i);
-    dnc = block_sum_int(dnc, s_i);
+    fixed = block_sum(fixed, s_i);
+    dnc = block_sum(dnc, s_i);
     if (threadIdx.x == 0) { xs->fix[0] = 0.0; xs->fix[1] = (double)dnc; xs->fix[2] = (double)fixed; }
 }
 
@@ -564,24 +301,12 @@ __global__ void scamp_sxr5(ScampK P, int t) {
     scamp_finish(P, t, (uint32_t)nc, (int)xs->fix[2], 0);
 }
 
-// Tracker (scamp.py:9-25): z = y, psi = 1, phi = inf, xmmse = 0
+// Tracker (scamp.py:9-25) and the record of iteration 0
 __global__ void scamp_init_kernel(ScampK P) {
-    const size_t BN_ = (size_t)P.B * P.N, Bn = (size_t)P.B * P.n, BL = (size_t)P.B * P.Lout;
-    const size_t tot = std::max(std::max(BN_, Bn), BL);
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < tot; e += (size_t)gridDim.x * blockDim.x) {
-        if (e < BN_) reinterpret_cast<float2*>(P.xm)[e] = make_float2(0.f, 0.f);
-        if (e < Bn) reinterpret_cast<float2*>(P.z)[e] = reinterpret_cast<const float2*>(P.y)[e];
-        if (e < (size_t)P.B * P.Lin) P.psi1[e] = 1.0f;
-        if (e < BL) P.phi[BL + e] = INFINITY;        // phi buffer of "iteration -1"
-        if (e < (size_t)P.B)                         // the pad of an odd n's s rows (scamp_sld)
-            for (int k = 2 * P.n; k < scamp_sld(P.n); ++k) P.s[e * scamp_sld(P.n) + k] = 0.f;
-    }
+    scamp_init_state(P);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         P.rcnt[0] = 0u; P.rcnt[1] = 0u;
-        ScampIter it;
-        it.stopped = 0; it.T = 0; it.fixed = 0; it.fixed_all = 0;
-        it.G = 0.0; it.slack = 0.0; it.notclose = 0; it.active = 0; it.pad[0] = it.pad[1] = 0;
-        P.iters[0] = it;
+        P.iters[0] = scamp_iter(0, 0, 0, 0, 0);
     }
 }
 
@@ -655,14 +380,7 @@ static void launch_ka(const ScampK& P, int gr, int t, hipStream_t st) {
 
 static void launch_kb(const ScampK& P, int gr, size_t ldsB, int t, hipStream_t st) {
     if (P.lx3) scamp_split(P, P.s, 2 * P.n, P.n, t, st);
-    switch (P.c.K) {
-    case 1: launch_kb_kk<1>(P, gr, ldsB, t, st); break;
-    case 2: launch_kb_kk<2>(P, gr, ldsB, t, st); break;
-    case 4: launch_kb_kk<4>(P, gr, ldsB, t, st); break;
-    case 8: launch_kb_kk<8>(P, gr, ldsB, t, st); break;
-    case 16: launch_kb_kk<16>(P, gr, ldsB, t, st); break;
-    default: launch_kb_kk<64>(P, gr, ldsB, t, st); break;
-    }
+    dispatch_K(P.c.K, [&](auto kk) { launch_kb_kk<decltype(kk)::value>(P, gr, ldsB, t, st); });
 }
 
 static int scamp_attrs() {
@@ -738,7 +456,7 @@ static int scamp_setup(const amp_dims* d, const amp_constellation* c, const amp_
     AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_scamp_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
     rc = scamp_attrs();
     if (rc) return rc;
-    scamp_geometry(d, P);
+    scamp_geometry(d, d->B, P);
     P.max_iter = a->max_iter;
     P.sigma2 = (float)a->noise_var;
     P.W = (const float*)a->W;
@@ -752,7 +470,7 @@ static int scamp_setup(const amp_dims* d, const amp_constellation* c, const amp_
     P.y = (const float*)a->y; P.z = w.z; P.s = w.s; P.phi = w.phi; P.tau = w.tau;
     P.xmap = (float*)a->xmap; P.xm = (float*)a->xmmse; P.psi0 = (float*)a->psi; P.psi1 = w.psi1;
     P.secmax = w.secmax; P.secabs = w.secabs; P.parts = w.parts; P.iters = w.iters; P.status = (amp_status*)a->status;
-    P.psi_nc = w.psi_nc; P.psi_nblk = scamp_psi_nblk(d); P.psi_split = scamp_psi_split(P.bn, P.Nt);
+    P.psi_nc = w.psi_nc; P.psi_nblk = scamp_psi_nblk(d);
     P.nwg = cdiv(d->B, 16);
     P.gen = 0;
     P.Wq1 = w.Wq1; P.Wq2 = w.Wq2; P.pparts = w.pparts; P.pxch = w.pxch; P.pbar = w.pbar;
@@ -826,13 +544,8 @@ static int scamp_prepare_impl(const ScampK& P, const amp_scamp_args* a, hipStrea
             if ((rc = h2_kband(P.WAH, 6, P.n / 32, P.bn / 32, P.ncpB / P.bn, P.N / 16, const_cast<int*>(P.bandB), st)))
                 return rc;
         }
-    } else {
-    if ((rc = build_cweight(A, P.N, 1, 0, nullptr, P.n, P.N, (float*)P.WA, P.kapA, P.ncpA, st))) return rc;
-    if ((rc = build_cweight(A, 1, P.N, 1, nullptr, P.N, P.n, (float*)P.WAH, P.kapB, P.ncpB, st))) return rc;
-    }
-    if (P.bandA && !P.lx3) {
-        if ((rc = weight_kband(P.WA, P.kapA, P.ncpA, 128, const_cast<int*>(P.bandA), st))) return rc;
-        if ((rc = weight_kband(P.WAH, P.kapB, P.ncpB, P.bn, const_cast<int*>(P.bandB), st))) return rc;
+    } else if ((rc = scamp_pack_f32(P, A, st))) {   // the f32 operators and their band ranges
+        return rc;
     }
     const size_t tot = std::max(std::max((size_t)P.B * P.N, (size_t)P.B * P.n), (size_t)P.B * P.Lout);
     hipLaunchKernelGGL(scamp_init_kernel, dim3((int)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, P);

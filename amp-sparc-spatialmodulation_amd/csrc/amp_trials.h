@@ -1,10 +1,13 @@
-// amp_trials.h — independent-trial batches (amp_vamp_trials_run / amp_bamp_trials_run): E
+// amp_trials.h — independent-trial batches (amp_vamp_trials_run / amp_bamp_trials_run /
+// amp_scamp_trials_run; the row guards below are also the launch engines', amp_bamp.h / amp_scamp.h): E
 // single-trial detections that share one channel and one SNR, run in one launch sequence.  Each
 // trial is the reference's B = 1 forward of that trial alone: at B = 1 the batch-global values
 // (var.mean() vamp.py:85, the max|xi| shift vamp.py:112 / bamp.py:70, the allclose exit
 // vamp.py:185 / bamp.py:140) are per-trial values, so every row of the GEMM tiles carries its own
 // iteration record and its own partials.
 #pragma once
+
+#include <type_traits>
 
 #include "amp_decide.h"
 #include "amp_denoise.h"
@@ -41,6 +44,49 @@ __device__ __forceinline__ bool tile_rows_live(const REC* recs, int row0, int ro
 #pragma unroll
     for (int i = 0; i < GBM; ++i) live |= s_stop[i] ^ 1;
     return live != 0;
+}
+
+// The row guard of a GEMM epilogue that the launch engine and the independent-trial engine share
+// (amp_bamp.h, amp_scamp.h): which rows of the tile it may store to.  The batch engine stores every
+// row (live() is a constant, the test folds away); the trial engine never stores to a stopped row
+// (s_stop: tile_rows_live's LDS flags).  PSCR: floats of partial-store scratch the epilogue keeps
+// free at the head of its LDS scratch, past the C tile (the trial engine stores one partial per row
+// while later rows still read the staged values; the batch engine stores one per tile, at the end).
+struct AllRows {
+    static constexpr int PSCR = 0;
+    __device__ __forceinline__ bool live(int) const { return true; }
+};
+struct LiveRows {
+    static constexpr int PSCR = 64;
+    const int* s_stop;
+    __device__ __forceinline__ bool live(int rho) const { return !s_stop[rho]; }
+};
+
+// Sum of an integer over the workgroup, returned to every thread (s: one word per wavefront).
+// Called by every thread; the leading barrier lets consecutive calls share s.
+template <class T>
+__device__ __forceinline__ T block_sum(T v, T* s) {
+    v = group_sum(v, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T tot = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s[w];
+    return tot;
+}
+
+// f(std::integral_constant<int, KK>) for the constellation size K as a compile-time bound
+// (check_dims: K in {1, 2, 4, 8, 16, 64})
+template <class F>
+inline void dispatch_K(int K, const F& f) {
+    switch (K) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    default: f(std::integral_constant<int, 64>{}); break;
+    }
 }
 
 // Per-trial decision + counters (amp_trials_decide.hip): Loss at B = 1 for each of `trials` rows

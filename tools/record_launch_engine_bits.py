@@ -1,0 +1,229 @@
+#!/usr/bin/env python3
+"""Records the bits of BAMP and SCAMP launch-engine forwards and forward_trials calls, with their
+inputs, as the fixture of tests/test_gpu_launch_engine_bits.py
+(tests/golden/launch_engine_bits.part<k>.npz).  The sibling of record_forward_bits.py (VAMP), whose
+storage conventions it keeps: row blocks of at most CHUNK bytes, parts of at most PART_LIMIT bytes.
+
+  python tools/record_launch_engine_bits.py [--out DIR]
+
+Public API only (Config, Channel, Data, BAMP, SCAMP), so the same script runs on any commit: a
+change that must leave both engines' results bit-identical is checked against a fixture recorded
+on its parent.  The inputs (A, W, y, x, sym, idx, SNR) are stored too: host BLAS is not pinned
+across machines.  One message of ROWS trials is drawn per (shape, alphabet); a batch case detects
+it at B = ROWS, a trials case detects its rows as ROWS independent B = 1 trials, BAMP and SCAMP
+cases of one shape share it.
+
+Every case runs twice and nothing is written unless the two runs agree in every bit.  A fix-up case
+scales one row's y until the forward reaches the exact float64 fix-up (nan_state 1, some but not
+all entries NaN) and stores the scale it used.
+"""
+import argparse
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, 'amp-sparc-spatialmodulation_amd'))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import numpy as np  # noqa: E402
+import torch        # noqa: E402
+
+import record_forward_bits as rfb  # noqa: E402  (chunked / save: the storage conventions)
+
+STEM = 'launch_engine_bits'
+ROWS = 40            # B of a batch case (two row tiles, the second partial), E of a trials case
+ITERATIONS = 20
+VICTIM = 5           # the row whose y a fix-up case scales
+SCALES = (30.0, 100.0, 300.0, 1e3, 3e3, 1e4, 1e5, 1e6)
+EBN0 = {'OOK': 8.0, 'BPSK': 8.0, 'QPSK': 6.0, '16QAM': 10.0}
+SEED = 29
+OUT_FIELDS = ('T', 'nan_state', 'counts', 'xmap', 'xmmse', 'state')   # state: var (BAMP) or psi (SCAMP)
+
+
+def case(det, dims, alphabet, kind, gemm='auto', mode='sparc', iterations=ITERATIONS, fixup=False, ebn0=None):
+    """dims = (Nt, Na, Nr, Lin, Lh) as Config takes them; kind: 'batch', 'trials' or 'b1' (B = 1);
+    ebn0: Eb/N0 in dB (default: the alphabet's, EBN0)."""
+    return dict(det=det, dims=tuple(dims), alphabet=alphabet, kind=kind, gemm=gemm, mode=mode, iterations=iterations,
+                fixup=fixup, ebn0=EBN0[alphabet] if ebn0 is None else float(ebn0))
+
+
+def _both(det, dims, alphabet, **kw):
+    return [case(det, dims, alphabet, 'batch', **kw), case(det, dims, alphabet, 'trials', **kw)]
+
+
+CASES = (
+    # BAMP f32: odd n, a partial last column tile, banded; (12, 3, 5, 2, 2): N % 4 == 2, the pair loader
+    _both('bamp', (6, 3, 5, 3, 1), 'OOK') + _both('bamp', (48, 6, 12, 2, 2), 'OOK') +
+    _both('bamp', (12, 3, 5, 2, 2), 'QPSK') +
+    # BAMP wide tile (bn = 256, M = 128), dense
+    _both('bamp', (256, 2, 32, 1, 1), 'QPSK') +
+    # BAMP split-precision forms
+    [case('bamp', (64, 4, 64, 1, 1), '16QAM', 'batch', gemm='x3'),
+     case('bamp', (64, 4, 64, 1, 1), '16QAM', 'batch', gemm='h2'),
+     # BAMP element-wise denoiser
+     case('bamp', (48, 6, 12, 2, 2), 'QPSK', 'b1', mode='random')] +
+    # SCAMP, psi formed in the tile
+    _both('scamp', (16, 4, 6, 2, 2), 'BPSK') + _both('scamp', (32, 4, 8, 2, 2), 'QPSK') +
+    # SCAMP, psi split: a block wider than a tile, a block boundary inside a tile
+    _both('scamp', (192, 12, 24, 3, 2), 'QPSK') + _both('scamp', (96, 6, 12, 4, 2), 'OOK') +
+    # SCAMP wide tile
+    _both('scamp', (256, 2, 32, 1, 1), 'QPSK') +
+    # SCAMP launch engine, bf16x3 tiles: at the alphabet's 10 dB the detector diverges (every entry NaN from
+    # the all-NaN rule), so also at 16 dB
+    [case('scamp', (64, 4, 64, 1, 1), '16QAM', 'batch', gemm='x3'),
+     case('scamp', (64, 4, 64, 1, 1), '16QAM', 'batch', gemm='x3', ebn0=16.0)] +
+    # the float64 fix-up, one row's y scaled
+    _both('bamp', (16, 4, 6, 2, 2), 'BPSK', iterations=2, fixup=True) +
+    _both('scamp', (16, 4, 6, 2, 2), 'BPSK', iterations=2, fixup=True)
+)
+
+
+def case_name(c):
+    tail = ''.join(f'_{v}' for v in (c['gemm'] if c['gemm'] != 'auto' else '', c['mode'] if c['mode'] != 'sparc' else '',
+                                     'fixup' if c['fixup'] else '',
+                                     f"{c['ebn0']:g}dB" if c['ebn0'] != EBN0[c['alphabet']] else '') if v)
+    return f"{c['det']}_{c['alphabet']}_{'_'.join(str(v) for v in c['dims'])}_{c['kind']}{tail}"
+
+
+def input_name(c):
+    rows = 1 if c['kind'] == 'b1' else ROWS
+    return f"in_{c['alphabet']}_{'_'.join(str(v) for v in c['dims'])}_{rows}_{c['mode']}_{c['ebn0']:g}dB"
+
+
+def config(c, batch, device):
+    from config import Config
+    return Config(*c['dims'], batch=batch, generator_mode=c['mode'], iterations=c['iterations'], alphabet=c['alphabet'],
+                  channel_profile='uniform', channel_truncation='tail', device=device)
+
+
+def make_inputs(c):
+    """One channel and one message of ROWS trials (1 for a 'b1' case), host arrays."""
+    from channel import Channel
+    from data import Data
+    np.random.seed(SEED)
+    torch.manual_seed(SEED)
+    cfg = config(c, 1 if c['kind'] == 'b1' else ROWS, 'cpu')
+    ch, da = Channel(cfg), Data(cfg)
+    W, A = ch.generate_as_sparc()
+    SNR = cfg.snr(c['ebn0'])
+    x, sym, idx = da.generate_message()
+    y = A @ x + ch.awgn(SNR)
+    return dict(A=rfb.as_np(A), W=rfb.as_np(W), SNR=np.array([SNR], dtype=np.float64), x=rfb.as_np(x)[..., 0],
+                y=rfb.as_np(y)[..., 0], sym=np.asarray(sym), idx=np.asarray(idx))
+
+
+def detector(c, batch):
+    import amp_native as nat
+    gemm = {'auto': nat.GEMM_AUTO, 'x3': nat.GEMM_X3, 'h2': nat.GEMM_H2}[c['gemm']]
+    cfg = config(c, batch, 'cuda')
+    if c['det'] == 'bamp':
+        from bamp import BAMP
+        return BAMP(cfg, gemm=gemm)
+    from scamp import SCAMP
+    return SCAMP(cfg, engine=nat.ENGINE_LAUNCHES, gemm=gemm)
+
+
+def _c(a):
+    return torch.view_as_real(a.reshape(a.shape[0], -1).contiguous()).cpu().numpy().copy()
+
+
+def run_case(c, inp, device, scale=1.0):
+    """The case's forward (or forward_trials) on the stored inputs: {field: array} of OUT_FIELDS and
+    'arith' (the arithmetic the Loss reports).  scale: the factor on row VICTIM's y."""
+    from loss import counts_to_vector
+    rows = inp['y'].shape[0]
+    y = torch.from_numpy(np.ascontiguousarray(inp['y'])).clone()
+    if scale != 1.0:
+        y[VICTIM] = y[VICTIM] * scale
+    y = y.to(device).unsqueeze(-1)
+    x = torch.from_numpy(np.ascontiguousarray(inp['x'])).to(device).unsqueeze(-1)
+    A = torch.from_numpy(np.ascontiguousarray(inp['A'])).to(device)
+    W = torch.from_numpy(np.ascontiguousarray(inp['W'])).to(device)
+    SNR = float(inp['SNR'][0])
+    chan = (A,) if c['det'] == 'bamp' else (W, A)
+    if c['kind'] == 'trials':
+        det = detector(c, 1)
+        S, N = inp['sym'].shape[0] // rows, x.shape[1]     # sections per trial; flat indices local to the trial
+        Ls = det.forward_trials(*chan, [y[e:e + 1] for e in range(rows)], SNR, [x[e:e + 1] for e in range(rows)],
+                                [inp['sym'][e * S:(e + 1) * S] for e in range(rows)],
+                                [inp['idx'][e * S:(e + 1) * S] - e * N for e in range(rows)])
+        for L in Ls:
+            L.resolve()
+        xmap, xm, state = (t.reshape(rows, -1) for t in det.last_trials)
+    else:
+        det = detector(c, rows)
+        Ls = [det(*chan, y, SNR, x, inp['sym'], inp['idx'])]
+        Ls[0].resolve()
+        b = det.last.buf
+        xmap, xm, state = b.xmap, b.xmmse, (b.var if c['det'] == 'bamp' else b.psi)
+    arith = {L.arithmetic for L in Ls}
+    assert len(arith) == 1, arith
+    return dict(T=np.array([int(L.last_status.T) for L in Ls], dtype=np.int64),
+                nan_state=np.array([int(L.last_status.nan_state) for L in Ls], dtype=np.int64),
+                counts=np.stack([np.asarray(counts_to_vector(L.last_counts)) for L in Ls]),
+                xmap=_c(xmap), xmmse=_c(xm), state=state.reshape(rows, -1).cpu().numpy().copy(),
+                arith=np.array([arith.pop()]))
+
+
+def differing(got, want):
+    """The fields of OUT_FIELDS (and 'arith') on which two results differ in a bit, with the first index."""
+    bad = []
+    for k in OUT_FIELDS + ('arith',):
+        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
+        if a.shape != b.shape or a.dtype != b.dtype:
+            bad.append(f'{k}: {a.dtype}{a.shape} != {b.dtype}{b.shape}')
+        elif a.tobytes() != b.tobytes():
+            ne = np.flatnonzero(a.reshape(-1).view(np.uint8) != b.reshape(-1).view(np.uint8))
+            i = int(ne[0]) // a.dtype.itemsize
+            bad.append(f'{k}: first difference at flat index {i} of {a.size} ({a.reshape(-1)[i]!r} != {b.reshape(-1)[i]!r})')
+    return bad
+
+
+def reaches_fixup(c, out):
+    """The exact fix-up ran and the all-NaN rule did not: nan_state 1 with some, not all, entries NaN
+    (a trials case: in the scaled trial; a batch case, whose shift and record are the batch's: in the batch)."""
+    nan = np.isnan(out['xmmse'][..., 0])
+    if c['kind'] == 'trials':
+        return int(out['nan_state'][VICTIM]) == 1 and 0 < int(nan[VICTIM].sum()) < nan.shape[1]
+    return int(out['nan_state'][0]) == 1 and 0 < int(nan.sum()) < nan.size
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(REPO, 'tests', 'golden'))
+    args = ap.parse_args()
+    device = torch.device('cuda', 0)
+    flat, inputs, unstable = {}, {}, []
+    for c in CASES:
+        name, iname = case_name(c), input_name(c)
+        if iname not in inputs:
+            inputs[iname] = make_inputs(c)
+            for k, v in inputs[iname].items():
+                flat[f'{iname}/{k}'] = v
+        inp = inputs[iname]
+        scale = 1.0
+        if c['fixup']:
+            for scale in SCALES:
+                if reaches_fixup(c, run_case(c, inp, device, scale)):
+                    break
+            else:
+                raise SystemExit(f'{name}: no scale of {SCALES} reaches the fix-up')
+            flat[f'{name}/scale'] = np.array([scale], dtype=np.float64)
+        first, second = run_case(c, inp, device, scale), run_case(c, inp, device, scale)
+        assert not c['fixup'] or reaches_fixup(c, first), name
+        bad = differing(second, first)
+        print(name, 'arith', str(first['arith']), 'scale', scale, 'T', first['T'].tolist(), 'nan_state',
+              sorted(set(first['nan_state'].tolist())), 'NaN entries', int(np.isnan(first['xmmse']).sum()),
+              'RUNS DIFFER: ' + '; '.join(bad) if bad else 'two runs equal', flush=True)
+        if bad:
+            unstable.append(name)
+        for k, v in first.items():
+            flat[f'{name}/{k}'] = v
+    if unstable:
+        raise SystemExit(f'no fixture written: two runs of {unstable} differ')
+    rfb.save(args.out, flat, STEM)
+
+
+if __name__ == '__main__':
+    main()
