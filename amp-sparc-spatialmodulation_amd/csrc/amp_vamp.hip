@@ -15,13 +15,18 @@
 //               leaves the normal range (amp_denoise.h, exact_section_f64); then the batch
 //               scalars of iteration t+1 (vamp.py:85-94, 66-82) or the stop record
 //               (vamp.py:185-186).  Later iterations of a stopped loop are no-ops.
+// The bodies (r~ loader, both epilogues, denoiser policy, Tracker, reduction step with its all-NaN
+// rule and float64 fix-up) are written once in amp_vamp_launch.h, shared with the independent-trial
+// engine (amp_vamp_trials.hip); the kernels here call them with the one record of iteration t
+// (VampAllRows).  The trial-sharded stages (vamp_xr1 .. xr4) use the same section loader, store,
+// all-NaN rule and commit.
 #include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <vector>
 
 #include "amp_persist.h"
-#include "amp_vamp.h"
+#include "amp_vamp_launch.h"
 
 namespace amp {
 
@@ -34,218 +39,48 @@ __global__ __launch_bounds__(RWG) void vamp_init_scalars(VampK P) {
     if (threadIdx.x == 0) P.iters[0] = it;
 }
 
-// r~ = (xmmse - dxdr * r) * normScalar (vamp.py:91), formed while loading GEMM1's A tile.
-// Staged in two steps like ALoadPlain (amp_gemm.h): both loads at a clamped address, the formula
-// and the zeroing of out-of-range elements at the LDS store.
-struct ALoadRt {
-    const float* __restrict__ xm;
-    const float* __restrict__ r;
-    int lda, rows, ka;
-    float dxdr, ns;
-    struct Raw {
-        float4 x, q;
-    };
-    __device__ __forceinline__ Raw raw(int row, int k) const {
-        const size_t o = (size_t)min(row, rows - 1) * lda + min(k, ka - 4);
-        return Raw{*reinterpret_cast<const float4*>(xm + o), *reinterpret_cast<const float4*>(r + o)};
-    }
-    __device__ __forceinline__ float4 fin(const Raw& v, int row, int k) const {
-        const bool ok = row < rows && k < ka;
-        const float4 x = v.x, q = v.q;
-        const float4 f = make_float4((x.x - dxdr * q.x) * ns, (x.y - dxdr * q.y) * ns, (x.z - dxdr * q.z) * ns,
-                                     (x.w - dxdr * q.w) * ns);
-        return ok ? f : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-};
-
 __global__ __launch_bounds__(AMP_WG) void vamp_k1(VampK P, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const VampIter it = P.iters[t];
-    if (it.stopped) return;
+    const VampAllRows g{P.iters[t]};
+    if (g.it.stopped) return;
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
-    const int twoN = 2 * P.N, twok = 2 * P.k;
-    gemm_tile<128>(ALoadRt{P.xm, P.r, twoN, P.B, twoN, it.dxdr_prev, it.ns_prev}, P.Wt1, P.kap1, row0, col0, lds);
-    using C = GemmCfg<128>;
-    // w = scale * (y~ + vr * q) - q   (vamp.py:68-72; `x_tilde - q` is what V @ consumes).  Every
-    // load of this thread's elements first, unconditional at a clamped index (the w stores may
-    // alias them as far as the compiler knows, and a branch around a load serialises the loads'
-    // latencies: amp_gemm.h ALoadPlain); out-of-range elements are never stored
-    constexpr int IT = GBM * 128 / AMP_WG;
-    float yv[IT], s2v[IT];
-#pragma unroll
-    for (int u = 0; u < IT; ++u) {
-        const int e = threadIdx.x + u * AMP_WG;
-        const int row = min(row0 + (e >> 7), P.B - 1), col = min(col0 + (e & 127), twok - 1);
-        yv[u] = P.ytil[(size_t)row * twok + col];
-        s2v[u] = P.s2[col >> 1];
-    }
-#pragma unroll
-    for (int u = 0; u < IT; ++u) {
-        const int e = threadIdx.x + u * AMP_WG;
-        const int rho = e >> 7, cc = e & 127;
-        const int row = row0 + rho, col = col0 + cc;
-        if (row < P.B && col < twok) {
-            const float q = lds[rho * C::LDC + cc];
-            const float sc = 1.0f / (s2v[u] + it.vr);
-            P.w[(size_t)row * P.wld + col] = sc * (yv[u] + it.vr * q) - q;
-        }
-    }
+    gemm_tile<128>(vamp_aload_rt(P, g, row0), P.Wt1, P.kap1, row0, col0, lds);
+    vamp_lmmse_epilogue(P, g, lds, row0, col0);
 }
-
-struct VampDenoisePolicy {
-    const float* tile;
-    int ldc, spr, M, N, L, row0, colc0;
-    float inv_sigma2;
-    float* xm;
-    float* var_new;
-    const float* var_prev;
-    float* secmax;
-    float* secabs;
-    __device__ __forceinline__ void load(int sec, int m, float& rr, float& ri, float& it) const {
-        const int rho = sec / spr, sj = sec - rho * spr;
-        const float2 v = *reinterpret_cast<const float2*>(tile + rho * ldc + 2 * (sj * M + m));
-        rr = v.x; ri = v.y; it = inv_sigma2;
-    }
-    __device__ __forceinline__ void store(int sec, int m, float xr, float xi, float var, PartAcc& pa) const {
-        const int rho = sec / spr, sj = sec - rho * spr;
-        const size_t o = (size_t)(row0 + rho) * N + colc0 + sj * M + m;
-        *reinterpret_cast<float2*>(xm + 2 * o) = make_float2(xr, xi);
-        var_new[o] = var;
-        pa.sumvar += (double)var;
-        pa.notclose += torch_close(var, var_prev[o]) ? 0u : 1u;     // vamp.py:185
-    }
-    __device__ __forceinline__ void section(int sec, float smax, float sabs) const {
-        const int rho = sec / spr, sj = sec - rho * spr;
-        const size_t o = (size_t)(row0 + rho) * L + (colc0 / M) + sj;
-        secmax[o] = smax;
-        secabs[o] = sabs;
-    }
-};
 
 template <int BN, int KK>
 __global__ __launch_bounds__(AMP_WG) void vamp_k2(VampK P, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const VampIter it = P.iters[t];
-    if (it.stopped) return;
-    using C = GemmCfg<BN>;
+    const VampAllRows g{P.iters[t]};
+    if (g.it.stopped) return;
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    const int twoN = 2 * P.N;
     gemm_tile<BN>(ALoadPlain{P.w, P.wld, P.B, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
-    // x~ = V w + r~ ; r = (x~ - alpha r~) / (1 - alpha)   (vamp.py:72, 79)
-    const int nrows = min(GBM, P.B - row0), ncols = min(BN, twoN - col0);
-    {
-        // every load of this thread's elements first, unconditional at a clamped index (see vamp_k1)
-        constexpr int IT = GBM * BN / AMP_WG;
-        float xv[IT], rv[IT];
-#pragma unroll
-        for (int u = 0; u < IT; ++u) {
-            const int e = threadIdx.x + u * AMP_WG;
-            const size_t o = (size_t)(row0 + min(e / BN, nrows - 1)) * twoN + col0 + min(e % BN, ncols - 1);
-            xv[u] = P.xm[o];
-            rv[u] = P.r[o];
-        }
-#pragma unroll
-        for (int u = 0; u < IT; ++u) {
-            const int e = threadIdx.x + u * AMP_WG;
-            const int rho = e / BN, cc = e % BN;
-            if (rho < nrows && cc < ncols) {
-                const size_t o = (size_t)(row0 + rho) * twoN + col0 + cc;
-                const float rt = (xv[u] - it.dxdr_prev * rv[u]) * it.ns_prev;
-                const float xt = lds[rho * C::LDC + cc] + rt;
-                const float rn = (xt - it.alpha * rt) * it.inv1ma;
-                P.r[o] = rn;
-                lds[rho * C::LDC + cc] = rn;
-            }
-        }
-    }
-    __syncthreads();
-    VampDenoisePolicy pol;
-    pol.tile = lds; pol.ldc = C::LDC; pol.M = P.M; pol.N = P.N; pol.L = P.L;
-    pol.spr = (ncols / 2) / P.M; pol.row0 = row0; pol.colc0 = col0 / 2;
-    pol.inv_sigma2 = it.inv_sigma2;
-    pol.xm = P.xm;
-    pol.var_new = var_buf(P, t);
-    pol.var_prev = var_buf(P, t + 1);
-    pol.secmax = P.secmax;
-    pol.secabs = P.secabs;
+    const int nrows = min(GBM, P.B - row0), ncols = min(BN, 2 * P.N - col0);
+    vamp_r_epilogue<BN>(P, g, lds, row0, col0, nrows, ncols);
+    // the denoiser over the whole tile; the workgroup's partial at its linear index
+    const VampDenoisePolicy pol = vamp_policy<BN>(P, g, t, lds, row0, col0, ncols, 0);
     PartAcc pa;
     denoise_sections<true, KK>(pol, nrows * pol.spr, P.M, P.c, pa);
-    part_block_store(pa, P.parts + (size_t)t * P.nblk2 + blockIdx.y * gridDim.x + blockIdx.x, lds + C::CTILE_FLOATS);
+    part_block_store(pa, P.parts + (size_t)t * P.nblk2 + blockIdx.y * gridDim.x + blockIdx.x,
+                     lds + GemmCfg<BN>::CTILE_FLOATS);
 }
+struct VampK2 {
+    template <int BN, int KK>
+    static constexpr auto fn() { return &vamp_k2<BN, KK>; }
+};
 
 // One workgroup after K2(t): partial reduction, exact float64 fix-up of out-of-range
 // sections, allclose decision and the scalars of iteration t+1.
 __global__ __launch_bounds__(RWG) void vamp_r(VampK P, Const64 c64, int t) {
     __shared__ __attribute__((aligned(16))) float lds[512];
-    __shared__ double s_fix[RWG / 64];
-    __shared__ unsigned s_nc[RWG / 64];
     const VampIter cur = P.iters[t];
     if (cur.stopped) {
         if (threadIdx.x == 0) P.iters[t + 1] = cur;
         return;
     }
-    PartAcc pa = part_reduce_all(P.parts + (size_t)t * P.nblk2, P.nblk2, lds);
-    int fixed = 0;
-    if (part_allnan(pa)) {
-        // the reference's G is NaN / inf: every section of this iteration is NaN
-        if (!cur.fixed_all) nan_fill(P.xm, var_buf(P, t), (size_t)P.B * P.N);
-        pa.sumvar = __longlong_as_double(0x7ff8000000000000LL);
-        pa.notclose = 1;
-        fixed = -1;
-    } else if (part_danger(pa)) {
-        // exact float64 G, then exact float64 recompute of every section below the danger
-        // line (rare); the recomputed values replace the fast-path ones in the reductions
-        float* vn = var_buf(P, t);
-        const float* vp = var_buf(P, t + 1);
-        const float inv = cur.inv_sigma2;
-        const float2* r2 = reinterpret_cast<const float2*>(P.r);
-        float2* x2 = reinterpret_cast<float2*>(P.xm);
-        const int M = P.M;
-        double dsum = 0.0;
-        int dnc = 0;
-        auto ldf = [=](int s) {
-            const size_t o0 = (size_t)s * M;
-            return [=](int m, float& rr, float& ri, float& it) {
-                const float2 v = r2[o0 + m];
-                rr = v.x; ri = v.y; it = inv;
-            };
-        };
-        auto stf = [&](int s) {
-            const size_t o0 = (size_t)s * M;
-            return [&, o0](int m, float xr, float xi, float var) {
-                const size_t o = o0 + m;
-                const float old = vn[o];
-                dsum += (double)var - (double)old;
-                dnc += (torch_close(var, vp[o]) ? 0 : 1) - (torch_close(old, vp[o]) ? 0 : 1);
-                x2[o] = make_float2(xr, xi);
-                vn[o] = var;
-            };
-        };
-        double G;
-        fixed = fixup_sections<true>(P.B * P.L, P.M, P.secmax, P.secabs, pa.maxabs, c64, ldf, stf, &G, s_fix);
-        pa.maxabs = G;
-        dsum = group_sum(dsum, 64);
-        dnc = group_sum(dnc, 64);
-        if ((threadIdx.x & 63) == 0) {
-            s_fix[threadIdx.x >> 6] = dsum;
-            s_nc[threadIdx.x >> 6] = (unsigned)dnc;
-        }
-        __syncthreads();
-        double d = 0.0;
-        unsigned nc = 0;
-        for (int w = 0; w < RWG / 64; ++w) { d += s_fix[w]; nc += s_nc[w]; }
-        // (sum - old) + new, in float64
-        pa.sumvar += d;
-        pa.notclose += nc;
-        __syncthreads();
-    }
-    const VampIter nx = vamp_advance(P, cur, pa, fixed, t, lds);
-    if (threadIdx.x == 0) {
-        P.iters[t + 1] = nx;
-        if (nx.stopped || t + 1 == P.max_iter) *P.status = vamp_make_status(P, cur, nx, fixed);
-    }
+    vamp_reduce(P, c64, cur, P.parts + (size_t)t * P.nblk2, P.nblk2, &P.iters[t + 1], P.status, t, lds);
 }
 
 // ---- trial-sharded iteration (amp_vamp_run_sharded; SURVEY §8(e) exact-compat mode) ----
@@ -299,19 +134,11 @@ __global__ __launch_bounds__(RWG) void vamp_xr2(VampK P, Const64 c64, int t) {
     PartAcc pa = xs_global(*xs);
     if (!part_allnan(pa) && part_danger(pa)) {
         // the rare path: this rank's exact float64 max|xi| over its candidate sections
-        const float inv = cur.inv_sigma2;
-        const float2* r2 = reinterpret_cast<const float2*>(P.r);
-        const int M = P.M;
         const double G32 = pa.maxabs, slack = logit_slack(G32);
         double gm = 0.0;
-        for (int s = threadIdx.x; s < P.B * P.L; s += blockDim.x) {
-            if (!((double)P.secabs[s] >= G32 - slack)) continue;
-            const size_t o0 = (size_t)s * M;
-            gm = fmax(gm, section_absmax_f64([=](int m, float& rr, float& ri, float& it) {
-                const float2 v = r2[o0 + m];
-                rr = v.x; ri = v.y; it = inv;
-            }, M, c64));
-        }
+        for (int s = threadIdx.x; s < P.B * P.L; s += blockDim.x)
+            if ((double)P.secabs[s] >= G32 - slack)
+                gm = fmax(gm, section_absmax_f64(vamp_section_load(P, cur, (size_t)s * P.M), P.M, c64));
         gm = group_max(gm, 64);
         double* sd = reinterpret_cast<double*>(lds);
         __syncthreads();
@@ -325,17 +152,10 @@ __global__ __launch_bounds__(RWG) void vamp_xr2(VampK P, Const64 c64, int t) {
         }
         return;
     }
-    int fixed = 0;
-    if (part_allnan(pa)) {
-        if (!cur.fixed_all) nan_fill(P.xm, var_buf(P, t), (size_t)P.B * P.N);
-        pa.sumvar = __longlong_as_double(0x7ff8000000000000LL);
-        pa.notclose = 1;
-        fixed = -1;
-    }
+    const int fixed = part_allnan(pa) ? vamp_allnan(P, cur, pa, t, P.B) : 0;
     const VampIter nx = vamp_advance(P, cur, pa, fixed, t, lds);
+    vamp_commit(P, &P.iters[t + 1], P.status, cur, nx, fixed, t);
     if (threadIdx.x == 0) {
-        P.iters[t + 1] = nx;
-        if (nx.stopped || t + 1 == P.max_iter) *P.status = vamp_make_status(P, cur, nx, fixed);
         xs->mode = 0;
         xs->gmax[0] = 0.0;
     }
@@ -351,32 +171,13 @@ __global__ __launch_bounds__(RWG) void vamp_xr3(VampK P, Const64 c64, int t) {
     const VampIter cur = P.iters[t];
     const PartAcc pa = xs_global(*xs);
     const double G = xs->gmax[0], slack = logit_slack(pa.maxabs);
-    float* vn = var_buf(P, t);
-    const float* vp = var_buf(P, t + 1);
-    const float inv = cur.inv_sigma2;
-    const float2* r2 = reinterpret_cast<const float2*>(P.r);
-    float2* x2 = reinterpret_cast<float2*>(P.xm);
-    const int M = P.M;
     double dsum = 0.0;
     int dnc = 0, cnt = 0;
     for (int s = threadIdx.x; s < P.B * P.L; s += blockDim.x) {
         if (!((double)P.secmax[s] - G < AMP_DANGER + slack)) continue;
         ++cnt;
-        const size_t o0 = (size_t)s * M;
-        exact_section_f64<true>(
-            [=](int m, float& rr, float& ri, float& it) {
-                const float2 v = r2[o0 + m];
-                rr = v.x; ri = v.y; it = inv;
-            },
-            [&](int m, float xr, float xi, float var) {
-                const size_t o = o0 + m;
-                const float old = vn[o];
-                dsum += (double)var - (double)old;
-                dnc += (torch_close(var, vp[o]) ? 0 : 1) - (torch_close(old, vp[o]) ? 0 : 1);
-                x2[o] = make_float2(xr, xi);
-                vn[o] = var;
-            },
-            M, c64, G);
+        const size_t o0 = (size_t)s * P.M;
+        exact_section_f64<true>(vamp_section_load(P, cur, o0), vamp_section_store(P, t, o0, &dsum, &dnc), P.M, c64, G);
     }
     dsum = group_sum(dsum, 64);
     dnc = group_sum(dnc, 64);
@@ -403,27 +204,10 @@ __global__ __launch_bounds__(RWG) void vamp_xr4(VampK P, int t) {
     pa.maxabs = xs->gmax[0];
     const int fixed = (int)xs->fix[2];
     const VampIter nx = vamp_advance(P, cur, pa, fixed, t, lds);
-    if (threadIdx.x == 0) {
-        P.iters[t + 1] = nx;
-        if (nx.stopped || t + 1 == P.max_iter) *P.status = vamp_make_status(P, cur, nx, fixed);
-    }
+    vamp_commit(P, &P.iters[t + 1], P.status, cur, nx, fixed, t);
 }
 
-__global__ void vamp_init_kernel(VampK P) {
-    // Tracker (vamp.py:22-26) in the form the fused kernels consume:
-    //   xmmse = p, r = 0 so that r~ = (xmmse - 0*r)*1 = p   (vamp.py:25)
-    //   var buffer 1 = ones: the `prev` of iteration 0      (vamp.py:24, 182)
-    const float p = (float)P.sparsity;
-    const size_t BN_ = (size_t)P.B * P.N;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < BN_; e += (size_t)gridDim.x * blockDim.x) {
-        reinterpret_cast<float2*>(P.xm)[e] = make_float2(p, 0.f);
-        reinterpret_cast<float2*>(P.r)[e] = make_float2(0.f, 0.f);
-        P.var1[e] = 1.0f;
-        if (e < (size_t)P.B)   // the pad of w's rows (vamp_wld), zeroed once: vamp_k1 stores columns < 2k only
-            for (int j = 2 * P.k; j < P.wld; ++j) P.w[e * P.wld + j] = 0.f;
-    }
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P.k; i += gridDim.x * blockDim.x) P.s2[i] = P.s[i] * P.s[i];
-}
+__global__ void vamp_init_kernel(VampK P) { vamp_init_state(P); }
 
 // The last executed iteration wrote var into buffer (T-1)&1; buffer 0 is the caller's.
 __global__ void vamp_output_kernel(VampK P) {
@@ -544,59 +328,18 @@ static int vamp_setup(const amp_dims* d, const amp_constellation* c, const amp_v
 static std::once_flag g_vamp_attr_once;
 static int g_vamp_attr_rc = 0;
 
-template <int KK>
-static int vamp_k2_attrs() {
-    int rc = set_lds_attr<128>((const void*)vamp_k2<128, KK>);
-    return rc ? rc : set_lds_attr<256>((const void*)vamp_k2<256, KK>);
-}
-
 static int vamp_attrs() {
     std::call_once(g_vamp_attr_once, [] {
-        int rc = set_lds_attr<128>((const void*)vamp_k1);
-        if (!rc) rc = vamp_k2_attrs<1>();
-        if (!rc) rc = vamp_k2_attrs<2>();
-        if (!rc) rc = vamp_k2_attrs<4>();
-        if (!rc) rc = vamp_k2_attrs<8>();
-        if (!rc) rc = vamp_k2_attrs<16>();
-        if (!rc) rc = vamp_k2_attrs<64>();
-        g_vamp_attr_rc = rc;
+        const int rc = set_lds_attr<128>((const void*)vamp_k1);
+        g_vamp_attr_rc = rc ? rc : vamp_k2_attrs<VampK2>();
     });
     return g_vamp_attr_rc;
 }
 
-template <int KK>
-static void launch_k2_kk(const VampK& P, int t, hipStream_t st) {
-    dim3 g2(cdiv(P.B, GBM), P.ncp2 / P.bn2);
-    if (P.bn2 == 128)
-        hipLaunchKernelGGL((vamp_k2<128, KK>), g2, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, t);
-    else
-        hipLaunchKernelGGL((vamp_k2<256, KK>), g2, dim3(AMP_WG), GemmCfg<256>::LDS_BYTES, st, P, t);
-}
-
-// GEMM2 + denoiser, instantiated per constellation size (K is validated by check_dims)
-static void launch_k2(const VampK& P, int t, hipStream_t st) {
-    switch (P.c.K) {
-    case 1: launch_k2_kk<1>(P, t, st); break;
-    case 2: launch_k2_kk<2>(P, t, st); break;
-    case 4: launch_k2_kk<4>(P, t, st); break;
-    case 8: launch_k2_kk<8>(P, t, st); break;
-    case 16: launch_k2_kk<16>(P, t, st); break;
-    default: launch_k2_kk<64>(P, t, st); break;
-    }
-}
-
-
 static int vamp_prepare_impl(const VampK& P, const amp_vamp_args* a, hipStream_t st) {
     int rc = vamp_attrs();
     if (rc) return rc;
-    // Wt0: y~ = (s * U^H) y        (vamp.py:22)    X[o][j] = s_o conj(U[j][o]),  o < k, j < n
-    rc = build_cweight((const float2*)a->U, 1, P.k, 1, P.s, P.k, P.n, (float*)P.Wt0, P.kap0, P.ncp0, st);
-    if (rc) return rc;
-    // Wt1: q = Vh r~               (vamp.py:67)    X[o][j] = Vh[o][j],           o < k, j < N
-    rc = build_cweight((const float2*)a->Vh, P.N, 1, 0, nullptr, P.k, P.N, (float*)P.Wt1, P.kap1, P.ncp1, st);
-    if (rc) return rc;
-    // Wt2: V (x~ - q), V = Vh^H    (vamp.py:19,72) X[o][j] = conj(Vh[j][o]),     o < N, j < k
-    rc = build_cweight((const float2*)a->Vh, 1, P.N, 1, nullptr, P.N, P.k, (float*)P.Wt2, P.kap2, P.ncp2, st);
+    rc = vamp_pack_f32(P, a, st);
     if (rc) return rc;
     const int g = (int)std::min<size_t>(((size_t)P.B * P.N + 255) / 256, 2048);
     hipLaunchKernelGGL(vamp_init_kernel, dim3(g), dim3(256), 0, st, P);
@@ -732,7 +475,7 @@ static int vamp_iterate_impl(const VampK& P, const Const64& c64, int t, hipStrea
     dim3 g1(cdiv(P.B, GBM), P.ncp1 / 128);
     hipLaunchKernelGGL(vamp_k1, g1, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, t);
     AMP_LAUNCH_CHECK("vamp_k1");
-    launch_k2(P, t, st);
+    vamp_k2_launch<VampK2>(P, st, t);
     AMP_LAUNCH_CHECK("vamp_k2");
     hipLaunchKernelGGL(vamp_r, dim3(1), dim3(RWG), 0, st, P, c64, t);
     AMP_LAUNCH_CHECK("vamp_r");
@@ -750,7 +493,7 @@ static int vamp_iterate_sharded(const VampK& P, const Const64& c64, int t, hipSt
     dim3 g1(cdiv(P.B, GBM), P.ncp1 / 128);
     hipLaunchKernelGGL(vamp_k1, g1, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, t);
     AMP_LAUNCH_CHECK("vamp_k1");
-    launch_k2(P, t, st);
+    vamp_k2_launch<VampK2>(P, st, t);
     AMP_LAUNCH_CHECK("vamp_k2");
     hipLaunchKernelGGL(vamp_xr1, dim3(1), dim3(RWG), 0, st, P, t);
     AMP_LAUNCH_CHECK("vamp_xr1");
@@ -1184,7 +927,7 @@ int amp_vamp_profile(const amp_dims* d, const amp_constellation* c, const amp_va
         (void)hipEventRecord(ev[1 + 3 * t], st);
         hipLaunchKernelGGL(vamp_k1, g1, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, t);
         (void)hipEventRecord(ev[2 + 3 * t], st);
-        launch_k2(P, t, st);
+        vamp_k2_launch<VampK2>(P, st, t);
         (void)hipEventRecord(ev[3 + 3 * t], st);
         hipLaunchKernelGGL(vamp_r, dim3(1), dim3(RWG), 0, st, P, c64, t);
     }

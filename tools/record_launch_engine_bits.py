@@ -1,21 +1,25 @@
 #!/usr/bin/env python3
-"""Records the bits of BAMP and SCAMP launch-engine forwards and forward_trials calls, with their
-inputs, as the fixture of tests/test_gpu_launch_engine_bits.py
-(tests/golden/launch_engine_bits.part<k>.npz).  The sibling of record_forward_bits.py (VAMP), whose
-storage conventions it keeps: row blocks of at most CHUNK bytes, parts of at most PART_LIMIT bytes.
+"""Records the bits of launch-engine forwards and forward_trials calls, with their inputs, as the
+fixtures of tests/test_gpu_launch_engine_bits.py: BAMP and SCAMP (CASES) as
+tests/golden/launch_engine_bits.part<k>.npz, VAMP (VAMP_CASES) as
+tests/golden/vamp_launch_bits.part<k>.npz.  The sibling of record_forward_bits.py (the persistent
+VAMP engine), whose storage conventions it keeps: row blocks of at most CHUNK bytes, parts of at
+most PART_LIMIT bytes.
 
-  python tools/record_launch_engine_bits.py [--out DIR]
+  python tools/record_launch_engine_bits.py [--out DIR] [--stem launch_engine_bits | vamp_launch_bits]
 
-Public API only (Config, Channel, Data, BAMP, SCAMP), so the same script runs on any commit: a
-change that must leave both engines' results bit-identical is checked against a fixture recorded
-on its parent.  The inputs (A, W, y, x, sym, idx, SNR) are stored too: host BLAS is not pinned
-across machines.  One message of ROWS trials is drawn per (shape, alphabet); a batch case detects
-it at B = ROWS, a trials case detects its rows as ROWS independent B = 1 trials, BAMP and SCAMP
-cases of one shape share it.
+Public API only (Config, Channel, Data, BAMP, SCAMP, VAMP, ShardedVAMP), so the same script runs on
+any commit: a change that must leave both engines' results bit-identical is checked against a
+fixture recorded on its parent.  The inputs (A, W or U, s, Vh; y, x, sym, idx, SNR) are stored too:
+host BLAS and LAPACK are not pinned across machines.  One message of ROWS trials is drawn per
+(shape, alphabet); a batch case detects it at B = ROWS, a trials case detects its rows as ROWS
+independent B = 1 trials, a sharded case (VAMP) detects it with ShardedVAMP in one process (the hook
+is the identity; the only way to the sharded kernels), the cases of one shape share it.
 
 Every case runs twice and nothing is written unless the two runs agree in every bit.  A fix-up case
 scales one row's y until the forward reaches the exact float64 fix-up (nan_state 1, some but not
-all entries NaN) and stores the scale it used.
+all entries NaN) and stores the scale it used.  An all-NaN case (VAMP) sets one row's y to NaN: the
+all-NaN rule makes every entry of the batch, or of that trial alone, NaN.
 """
 import argparse
 import os
@@ -32,20 +36,25 @@ import torch        # noqa: E402
 import record_forward_bits as rfb  # noqa: E402  (chunked / save: the storage conventions)
 
 STEM = 'launch_engine_bits'
+VAMP_STEM = 'vamp_launch_bits'
 ROWS = 40            # B of a batch case (two row tiles, the second partial), E of a trials case
 ITERATIONS = 20
 VICTIM = 5           # the row whose y a fix-up case scales
 SCALES = (30.0, 100.0, 300.0, 1e3, 3e3, 1e4, 1e5, 1e6)
-EBN0 = {'OOK': 8.0, 'BPSK': 8.0, 'QPSK': 6.0, '16QAM': 10.0}
+# VAMP: the window between "no section leaves the normal range" and "every entry NaN" is narrow
+VAMP_SCALES = tuple(float(v) for v in range(30, 100, 5)) + tuple(float(v) for v in range(100, 1001, 50)) + SCALES[3:]
+EBN0 = {'OOK': 8.0, 'BPSK': 8.0, 'QPSK': 6.0, '8PSK': 8.0, '16QAM': 10.0}
 SEED = 29
 OUT_FIELDS = ('T', 'nan_state', 'counts', 'xmap', 'xmmse', 'state')   # state: var (BAMP) or psi (SCAMP)
+VAMP_OUT_FIELDS = ('T', 'nan_state', 'counts', 'r', 'xmmse', 'var')
 
 
-def case(det, dims, alphabet, kind, gemm='auto', mode='sparc', iterations=ITERATIONS, fixup=False, ebn0=None):
-    """dims = (Nt, Na, Nr, Lin, Lh) as Config takes them; kind: 'batch', 'trials' or 'b1' (B = 1);
-    ebn0: Eb/N0 in dB (default: the alphabet's, EBN0)."""
+def case(det, dims, alphabet, kind, gemm='auto', mode='sparc', iterations=ITERATIONS, fixup=False, ebn0=None,
+         allnan=False):
+    """dims = (Nt, Na, Nr, Lin, Lh) as Config takes them; kind: 'batch', 'trials', 'b1' (B = 1) or
+    'sharded' (VAMP); ebn0: Eb/N0 in dB (default: the alphabet's, EBN0); allnan: row VICTIM's y is NaN."""
     return dict(det=det, dims=tuple(dims), alphabet=alphabet, kind=kind, gemm=gemm, mode=mode, iterations=iterations,
-                fixup=fixup, ebn0=EBN0[alphabet] if ebn0 is None else float(ebn0))
+                fixup=fixup, ebn0=EBN0[alphabet] if ebn0 is None else float(ebn0), allnan=allnan)
 
 
 def _both(det, dims, alphabet, **kw):
@@ -79,16 +88,46 @@ CASES = (
 )
 
 
+def _vamp(dims, alphabet, kinds=('batch', 'trials', 'sharded'), **kw):
+    return [case('vamp', dims, alphabet, kind, **kw) for kind in kinds]
+
+
+# VAMP launch engine (GEMM_F32), its trial engine and its sharded form (vamp_xr1 .. xr4)
+VAMP_CASES = (
+    # K = 1, odd n = k = 15 (the pair loader for y, w's padded stride), a partial last column tile
+    _vamp((6, 3, 5, 3, 1), 'OOK') +
+    # K = 4, odd k; at 10 dB the trials exit at odd and at even T
+    _vamp((12, 3, 5, 2, 2), 'QPSK', ebn0=10.0) +
+    # K = 2, n > N so k = N
+    _vamp((8, 2, 11, 1, 1), 'BPSK') +
+    # K = 8, M = 2, odd n = k = 27
+    _vamp((24, 12, 9, 2, 2), '8PSK') +
+    # M = 128: the 256-column tile of K2
+    _vamp((256, 2, 32, 1, 1), 'QPSK') +
+    # K = 16, a persistent-eligible shape forced onto the launch engine
+    _vamp((64, 4, 64, 1, 1), '16QAM', kinds=('batch', 'trials')) +
+    # the exact float64 fix-up (sharded: the rare path of vamp_xr2 .. xr4), one row's y scaled
+    _vamp((16, 2, 7, 4, 2), 'OOK', iterations=2, fixup=True) +
+    # the all-NaN rule, one row's y NaN
+    _vamp((16, 2, 7, 4, 2), 'OOK', iterations=2, allnan=True)
+)
+
+
+def out_fields(c):
+    return VAMP_OUT_FIELDS if c['det'] == 'vamp' else OUT_FIELDS
+
+
 def case_name(c):
     tail = ''.join(f'_{v}' for v in (c['gemm'] if c['gemm'] != 'auto' else '', c['mode'] if c['mode'] != 'sparc' else '',
-                                     'fixup' if c['fixup'] else '',
+                                     'fixup' if c['fixup'] else '', 'allnan' if c.get('allnan') else '',
                                      f"{c['ebn0']:g}dB" if c['ebn0'] != EBN0[c['alphabet']] else '') if v)
     return f"{c['det']}_{c['alphabet']}_{'_'.join(str(v) for v in c['dims'])}_{c['kind']}{tail}"
 
 
 def input_name(c):
     rows = 1 if c['kind'] == 'b1' else ROWS
-    return f"in_{c['alphabet']}_{'_'.join(str(v) for v in c['dims'])}_{rows}_{c['mode']}_{c['ebn0']:g}dB"
+    det = 'vamp_' if c['det'] == 'vamp' else ''
+    return f"in_{det}{c['alphabet']}_{'_'.join(str(v) for v in c['dims'])}_{rows}_{c['mode']}_{c['ebn0']:g}dB"
 
 
 def config(c, batch, device):
@@ -109,6 +148,10 @@ def make_inputs(c):
     SNR = cfg.snr(c['ebn0'])
     x, sym, idx = da.generate_message()
     y = A @ x + ch.awgn(SNR)
+    if c['det'] == 'vamp':
+        U, s, Vh = torch.linalg.svd(A, full_matrices=False)
+        return dict(U=rfb.as_np(U), s=rfb.as_np(s), Vh=rfb.as_np(Vh), SNR=np.array([SNR], dtype=np.float64),
+                    x=rfb.as_np(x)[..., 0], y=rfb.as_np(y)[..., 0], sym=np.asarray(sym), idx=np.asarray(idx))
     return dict(A=rfb.as_np(A), W=rfb.as_np(W), SNR=np.array([SNR], dtype=np.float64), x=rfb.as_np(x)[..., 0],
                 y=rfb.as_np(y)[..., 0], sym=np.asarray(sym), idx=np.asarray(idx))
 
@@ -117,6 +160,9 @@ def detector(c, batch):
     import amp_native as nat
     gemm = {'auto': nat.GEMM_AUTO, 'x3': nat.GEMM_X3, 'h2': nat.GEMM_H2}[c['gemm']]
     cfg = config(c, batch, 'cuda')
+    if c['det'] == 'vamp':
+        from vamp import VAMP, ShardedVAMP
+        return ShardedVAMP(cfg) if c['kind'] == 'sharded' else VAMP(cfg, engine=nat.ENGINE_LAUNCHES, gemm=nat.GEMM_F32)
     if c['det'] == 'bamp':
         from bamp import BAMP
         return BAMP(cfg, gemm=gemm)
@@ -129,19 +175,21 @@ def _c(a):
 
 
 def run_case(c, inp, device, scale=1.0):
-    """The case's forward (or forward_trials) on the stored inputs: {field: array} of OUT_FIELDS and
+    """The case's forward (or forward_trials) on the stored inputs: {field: array} of out_fields(c) and
     'arith' (the arithmetic the Loss reports).  scale: the factor on row VICTIM's y."""
     from loss import counts_to_vector
     rows = inp['y'].shape[0]
     y = torch.from_numpy(np.ascontiguousarray(inp['y'])).clone()
     if scale != 1.0:
         y[VICTIM] = y[VICTIM] * scale
+    if c.get('allnan'):
+        y[VICTIM] = complex(float('nan'), float('nan'))
     y = y.to(device).unsqueeze(-1)
     x = torch.from_numpy(np.ascontiguousarray(inp['x'])).to(device).unsqueeze(-1)
-    A = torch.from_numpy(np.ascontiguousarray(inp['A'])).to(device)
-    W = torch.from_numpy(np.ascontiguousarray(inp['W'])).to(device)
+    dev = lambda k: torch.from_numpy(np.ascontiguousarray(inp[k])).to(device)  # noqa: E731
     SNR = float(inp['SNR'][0])
-    chan = (A,) if c['det'] == 'bamp' else (W, A)
+    chan = {'vamp': ('U', 's', 'Vh'), 'bamp': ('A',), 'scamp': ('W', 'A')}[c['det']]
+    chan = tuple(dev(k) for k in chan)
     if c['kind'] == 'trials':
         det = detector(c, 1)
         S, N = inp['sym'].shape[0] // rows, x.shape[1]     # sections per trial; flat indices local to the trial
@@ -150,26 +198,30 @@ def run_case(c, inp, device, scale=1.0):
                                 [inp['idx'][e * S:(e + 1) * S] - e * N for e in range(rows)])
         for L in Ls:
             L.resolve()
-        xmap, xm, state = (t.reshape(rows, -1) for t in det.last_trials)
+        xmap, xm, state = (t.reshape(rows, -1) for t in det.last_trials)     # VAMP: r, xmmse, var
     else:
         det = detector(c, rows)
         Ls = [det(*chan, y, SNR, x, inp['sym'], inp['idx'])]
         Ls[0].resolve()
-        b = det.last.buf
-        xmap, xm, state = b.xmap, b.xmmse, (b.var if c['det'] == 'bamp' else b.psi)
+        if c['det'] == 'vamp':
+            xmap, xm, state = det.last_shard if c['kind'] == 'sharded' else (det.last.r, det.last.xmmse, det.last.var)
+        else:
+            b = det.last.buf
+            xmap, xm, state = b.xmap, b.xmmse, (b.var if c['det'] == 'bamp' else b.psi)
     arith = {L.arithmetic for L in Ls}
     assert len(arith) == 1, arith
-    return dict(T=np.array([int(L.last_status.T) for L in Ls], dtype=np.int64),
-                nan_state=np.array([int(L.last_status.nan_state) for L in Ls], dtype=np.int64),
-                counts=np.stack([np.asarray(counts_to_vector(L.last_counts)) for L in Ls]),
-                xmap=_c(xmap), xmmse=_c(xm), state=state.reshape(rows, -1).cpu().numpy().copy(),
-                arith=np.array([arith.pop()]))
+    first, state_name = ('r', 'var') if c['det'] == 'vamp' else ('xmap', 'state')
+    return {'T': np.array([int(L.last_status.T) for L in Ls], dtype=np.int64),
+            'nan_state': np.array([int(L.last_status.nan_state) for L in Ls], dtype=np.int64),
+            'counts': np.stack([np.asarray(counts_to_vector(L.last_counts)) for L in Ls]),
+            first: _c(xmap), 'xmmse': _c(xm), state_name: state.reshape(rows, -1).cpu().numpy().copy(),
+            'arith': np.array([arith.pop()])}
 
 
 def differing(got, want):
-    """The fields of OUT_FIELDS (and 'arith') on which two results differ in a bit, with the first index."""
+    """The fields (and 'arith') on which two results differ in a bit, with the first index."""
     bad = []
-    for k in OUT_FIELDS + ('arith',):
+    for k in got:
         a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
         if a.shape != b.shape or a.dtype != b.dtype:
             bad.append(f'{k}: {a.dtype}{a.shape} != {b.dtype}{b.shape}')
@@ -189,13 +241,23 @@ def reaches_fixup(c, out):
     return int(out['nan_state'][0]) == 1 and 0 < int(nan.sum()) < nan.size
 
 
+def all_nan_rule(c, out):
+    """The all-NaN rule ran: every entry of the batch (batch, sharded) or of trial VICTIM and of no other
+    trial (trials) is NaN."""
+    nan = np.isnan(out['xmmse'][..., 0])
+    if c['kind'] == 'trials':
+        return bool(nan[VICTIM].all()) and int(nan.sum()) == nan.shape[1]
+    return bool(nan.all())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(REPO, 'tests', 'golden'))
+    ap.add_argument('--stem', default=STEM, choices=(STEM, VAMP_STEM))
     args = ap.parse_args()
     device = torch.device('cuda', 0)
     flat, inputs, unstable = {}, {}, []
-    for c in CASES:
+    for c in (VAMP_CASES if args.stem == VAMP_STEM else CASES):
         name, iname = case_name(c), input_name(c)
         if iname not in inputs:
             inputs[iname] = make_inputs(c)
@@ -204,14 +266,16 @@ def main():
         inp = inputs[iname]
         scale = 1.0
         if c['fixup']:
-            for scale in SCALES:
+            scales = VAMP_SCALES if c['det'] == 'vamp' else SCALES
+            for scale in scales:
                 if reaches_fixup(c, run_case(c, inp, device, scale)):
                     break
             else:
-                raise SystemExit(f'{name}: no scale of {SCALES} reaches the fix-up')
+                raise SystemExit(f'{name}: no scale of {scales} reaches the fix-up')
             flat[f'{name}/scale'] = np.array([scale], dtype=np.float64)
         first, second = run_case(c, inp, device, scale), run_case(c, inp, device, scale)
         assert not c['fixup'] or reaches_fixup(c, first), name
+        assert not c.get('allnan') or all_nan_rule(c, first), name
         bad = differing(second, first)
         print(name, 'arith', str(first['arith']), 'scale', scale, 'T', first['T'].tolist(), 'nan_state',
               sorted(set(first['nan_state'].tolist())), 'NaN entries', int(np.isnan(first['xmmse']).sum()),
@@ -222,7 +286,7 @@ def main():
             flat[f'{name}/{k}'] = v
     if unstable:
         raise SystemExit(f'no fixture written: two runs of {unstable} differ')
-    rfb.save(args.out, flat, STEM)
+    rfb.save(args.out, flat, args.stem)
 
 
 if __name__ == '__main__':
