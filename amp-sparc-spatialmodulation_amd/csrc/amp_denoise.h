@@ -815,9 +815,243 @@ __device__ __forceinline__ void denoise_step_grid2_full(const P& pol, int base, 
     }
 }
 
+// The full-round step at G = 32 with the two halves of every f2v on positions 2j and 2j + 1 of ONE
+// section (16 lanes per section; a wave step covers the same four sections base .. base + 3, section
+// base + q in lanes 16 q .. 16 q + 15).  Every section reduction then runs once per step instead of
+// once per half, its first butterfly step is an in-lane operation and the other four stay inside one
+// DPP row (no permlane), one v_rcp_f32 serves both positions, and the policy moves a position pair
+// per access (load_r2 / load_prev2 / store_xv2).
+//
+// grid2_pair_core restates grid2_core with ur, ui, X, Y, er, ei, f, zt, ar, ai, var over the lane's
+// two positions: every per-position operation keeps its operands, type and order.  A copy, like
+// grid2_core itself.  The section reductions keep group_fmax_c<32>'s and
+// group_sum_excl_c<32>'s results bit for bit:
+//   max   an integer max over fkey keys is exact and order-free; the in-lane step is an integer max
+//         too (v_max_f32 would drop a NaN);
+//   sums  group_sum_excl_c<32> runs xor 1, 2, 4, 8, 16 over positions, and its first step pairs
+//         exactly positions 2j and 2j + 1: with a, b the lane's two values, excl_a = 0 + b,
+//         excl_b = 0 + a, tot = a + b, then the DPP distances 1, 2, 4, 8 over j are the old
+//         2, 4, 8, 16 (float addition is commutative: the same tree term for term).
+template <bool kVar, int R, int PAT>
+__device__ __forceinline__ void grid2_pair_core(const f2v ur, const f2v ui, const GridRegs<R>& Q, f2v& xr_out, f2v& xi_out,
+                                                f2v& var_out, float& smax_out, float& sabs_out) {
+    constexpr bool FULLG = PAT == GRID_FULL;
+    f2v X[R], Y[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        X[i] = ur * f2splat(Q.re[i]);
+        Y[i] = ui * f2splat(Q.im[i]);
+    }
+    f2v mx, my, lmx, lab;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        float ax = -FLT_MAX, nx = FLT_MAX, ay = -FLT_MAX, ny = FLT_MAX;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            ax = fmaxf(ax, X[i][u]); nx = fminf(nx, X[i][u]);
+            ay = fmaxf(ay, Y[i][u]); ny = fminf(ny, Y[i][u]);
+        }
+        mx[u] = ax; my[u] = ay;
+        lmx[u] = ax + ay;                          // max logit of the position (a corner)
+        lab[u] = fmaxf(lmx[u], -(nx + ny));        // max |logit| of the position
+    }
+    int kmax = max(fkey(lmx.x), fkey(lmx.y)), kabs = max(fkey(lab.x), fkey(lab.y));
+    kmax = imax_step<1>(kmax); kabs = imax_step<1>(kabs);
+    kmax = imax_step<2>(kmax); kabs = imax_step<2>(kabs);
+    kmax = imax_step<4>(kmax); kabs = imax_step<4>(kabs);
+    kmax = imax_step<8>(kmax); kabs = imax_step<8>(kabs);
+    const float smax1 = funkey(kmax), sabs1 = funkey(kabs);
+    const f2v smax = f2splat(smax1);
+    const f2v l2e = f2splat(AMP_LOG2E);
+#if AMP_DEN_EXACT_EXP
+    f2v f = {den_exp(lmx.x, smax.x), den_exp(lmx.y, smax.y)};
+#else
+    f2v targ = (lmx - smax) * l2e;
+    f2v f = {__builtin_amdgcn_exp2f(targ.x), __builtin_amdgcn_exp2f(targ.y)};
+#endif
+    f2v er[R], ei[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+#if AMP_DEN_EXACT_EXP
+        er[i] = f2v{den_exp(X[i].x, mx.x), den_exp(X[i].y, mx.y)};
+        ei[i] = f2v{den_exp(Y[i].x, my.x), den_exp(Y[i].y, my.y)};
+#else
+        const f2v xa = (X[i] - mx) * l2e, ya = (Y[i] - my) * l2e;
+        er[i] = f2v{__builtin_amdgcn_exp2f(xa.x), __builtin_amdgcn_exp2f(xa.y)};
+        ei[i] = f2v{__builtin_amdgcn_exp2f(ya.x), __builtin_amdgcn_exp2f(ya.y)};
+#endif
+    }
+    f2v zt, ar, ai, SI = f2splat(0.f);
+    f2v Sr[FULLG ? 1 : R];
+    if constexpr (FULLG) {
+        f2v sr = f2splat(0.f), si = f2splat(0.f), a = f2splat(0.f), b = f2splat(0.f);
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            sr += er[i]; si += ei[i];
+            a = f2fma(f2splat(Q.re[i]), er[i], a);
+            b = f2fma(f2splat(Q.im[i]), ei[i], b);
+        }
+        SI = si; Sr[0] = sr;
+        zt = (sr * si) * f;
+        ar = (a * si) * f;
+        ai = (sr * b) * f;
+    } else {
+        f2v z = f2splat(0.f), a = f2splat(0.f), b = f2splat(0.f), w[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) w[j] = f2splat(Q.im[j]) * ei[j];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            f2v si = f2splat(0.f), ti = f2splat(0.f);
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const float cw = grid_cnt<PAT>(i, j);
+                if (cw == 1.f) { si += ei[j]; ti += w[j]; }
+                else if (cw == 2.f) { si = f2fma(f2splat(2.f), ei[j], si); ti = f2fma(f2splat(2.f), w[j], ti); }
+            }
+            Sr[i] = si;
+            const f2v es = er[i] * si;
+            z += es;
+            a = f2fma(f2splat(Q.re[i]), es, a);
+            b = f2fma(er[i], ti, b);
+        }
+        zt = z * f;
+        ar = a * f;
+        ai = b * f;
+    }
+    // Z and the exclusive sums: group_sum_excl_c<32>'s tree, its xor-1 step in the lane
+    float tot = zt.x + zt.y;
+    f2v zev = {0.f + zt.y, 0.f + zt.x};
+    {
+        float p = xl<1>(tot);
+        zev.x += p; zev.y += p; tot = tot + p;
+        p = xl<2>(tot);
+        zev.x += p; zev.y += p; tot = tot + p;
+        p = xl<4>(tot);
+        zev.x += p; zev.y += p; tot = tot + p;
+        p = xl<8>(tot);
+        zev.x += p; zev.y += p; tot = tot + p;
+    }
+    const f2v iz = f2splat(den_rcp(tot));
+    const f2v xr = ar * iz, xi = ai * iz;
+    f2v var = f2splat(0.f);
+    if (kVar) {
+        f2v vs;
+        if constexpr (FULLG) {
+            f2v vr = f2splat(0.f), vi = f2splat(0.f);
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                const f2v dr = xr - f2splat(Q.re[i]), di = xi - f2splat(Q.im[i]);
+                vr = f2fma(dr * dr, er[i], vr);
+                vi = f2fma(di * di, ei[i], vi);
+            }
+            vs = f2fma(vr, SI, Sr[0] * vi) * f;
+        } else {
+            f2v d[R];
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const f2v di = xi - f2splat(Q.im[j]);
+                d[j] = (di * di) * ei[j];
+            }
+            f2v acc = f2splat(0.f);
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                f2v vi = f2splat(0.f);
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    const float cw = grid_cnt<PAT>(i, j);
+                    if (cw == 1.f) vi += d[j];
+                    else if (cw == 2.f) vi = f2fma(f2splat(2.f), d[j], vi);
+                }
+                const f2v dr = xr - f2splat(Q.re[i]);
+                acc = f2fma(er[i], f2fma(dr * dr, Sr[i], vi), acc);
+            }
+            vs = acc * f;
+        }
+        var = (xr * xr + xi * xi) * (zev * iz) + vs * iz;
+    }
+    xr_out = xr; xi_out = xi; var_out = var; smax_out = smax1; sabs_out = sabs1;
+}
+
+// sumvar is a float64 sum whose order reaches the batch mean, so the pair step keeps the old
+// chains.  Old lane (gid, g) of the 32-lane map adds, per step, var[base + gid][g] and then
+// var[base + 2 + gid][g].  In the pair map lane n < 32 holds positions 2j, 2j + 1 (j = n & 15) of
+// section base + (n >> 4) and lane n + 32 the same positions of section base + 2 + (n >> 4): one
+// v_permlane32_swap of (var.x, var.y) leaves lane n with var.x of both sections and lane n + 32
+// with var.y of both, so pair lane n carries the chain of old lane
+//   (n >> 4 & 1) * 32 + 2 (n & 15) + (n >> 5)
+// in one float64 accumulator, with the old two additions per step.  pair_acc_in / pair_acc_out move
+// the accumulators between the maps (once per denoiser call), so that steps of the 32-lane map
+// before or after (the masked remainder) continue the same chains and part_wave_reduce's tree is
+// the one it was.
+__device__ __forceinline__ double pair_acc_move(double v, int src_lane) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_ds_bpermute(4 * src_lane, (int)(unsigned)b);
+    const int hi = __builtin_amdgcn_ds_bpermute(4 * src_lane, (int)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+// (the lane index goes through an empty asm so that the source lane is formed where it is used:
+// hoisted to the kernel's start it is one more value held, or spilled, across the whole loop)
+__device__ __forceinline__ int pair_lane() {
+    int l = threadIdx.x & 63;
+    asm volatile("" : "+v"(l));
+    return l;
+}
+__device__ __forceinline__ double pair_acc_in(double sumvar) {   // 32-lane map -> pair map
+    const int n = pair_lane();
+    return pair_acc_move(sumvar, ((n >> 4) & 1) * 32 + 2 * (n & 15) + (n >> 5));
+}
+__device__ __forceinline__ double pair_acc_out(double acc) {     // pair map -> 32-lane map
+    const int l = pair_lane();
+    return pair_acc_move(acc, (l & 1) * 32 + (l >> 5) * 16 + ((l & 31) >> 1));
+}
+
+struct GridPairIn {
+    f2v rr, ri, vp;   // the lane's two positions: r (re, im) and the previous variances
+};
+template <class P>
+__device__ __forceinline__ GridPairIn grid2_pair_load(const P& pol, int base, int lane) {
+    const int sec = base + (lane >> 4), m = 2 * (lane & 15);
+    GridPairIn in;
+    const float4 v = pol.load_r2(sec, m);
+    const float2 p = pol.load_prev2(sec, m);
+    in.rr = f2v{v.x, v.z}; in.ri = f2v{v.y, v.w};
+    in.vp = f2v{p.x, p.y};
+    // both loads issued here and waited for together (left alone, the previous variances' load sinks
+    // to its use, the step's last instructions, and its latency stands before the stores)
+    asm volatile("" : "+v"(in.vp));
+    return in;
+}
+template <bool kVar, int R, int PAT, class P>
+__device__ __forceinline__ void denoise_step_grid2_pair(const P& pol, int base, int lane, const GridPairIn& in,
+                                                        const GridRegs<R>& Q, PartAcc& pa, double& acc, DenStat& S) {
+    const int sec = base + (lane >> 4), m = 2 * (lane & 15);
+    const f2v it = f2splat(pol.inv);
+    const f2v ur = in.rr * it, ui = in.ri * it;   // c64 / f32 == multiply by the reciprocal
+    const int bad = (int)!(fabsf(ur.x) <= FLT_MAX) | (int)!(fabsf(ui.x) <= FLT_MAX) | (int)!(fabsf(ur.y) <= FLT_MAX) |
+                    (int)!(fabsf(ui.y) <= FLT_MAX);
+    S.st_bad |= bad != 0;
+    f2v xr, xi, var;
+    float smax, sabs;
+    grid2_pair_core<kVar, R, PAT>(ur, ui, Q, xr, xi, var, smax, sabs);
+    pol.store_xv2(sec, m, make_float4(xr.x, xi.x, xr.y, xi.y), make_float2(var.x, var.y));
+    // lanes < 32: var.x of sections base + gid, base + 2 + gid; lanes >= 32: var.y of the same two
+    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(var.x), __float_as_uint(var.y), false, false);
+    acc += (double)__uint_as_float(sw[0]);
+    acc += (double)__uint_as_float(sw[1]);
+    pol.account_close(var.x, in.vp.x, pa);
+    pol.account_close(var.y, in.vp.y, pa);
+    S.st_abs = nan_max(S.st_abs, sabs);
+    S.st_min = nan_min(S.st_min, smax);
+    pol.section(sec, smax, sabs);
+}
+
 #ifndef AMP_DEN_PACKED_GRID
 #define AMP_DEN_PACKED_GRID 1
 #endif
+
+// denoise_sections_grid's FAST: DEN_FAST_FULL the full-round step, DEN_FAST_PAIR the same with the
+// position-pair step where G = 32 and the grid is the packed GRID_REF16 (any other G: DEN_FAST_FULL).
+enum { DEN_FAST_NONE = 0, DEN_FAST_FULL = 1, DEN_FAST_PAIR = 2 };
 
 // Grid dimension of a compile-time constellation size (0: no product-grid form).
 template <int KK>
@@ -828,9 +1062,11 @@ constexpr int grid_r() { return KK == 4 ? 2 : KK == 16 ? 4 : KK == 64 ? 8 : 0; }
 // FAST (with the packed grid, U = 2; the policy supplies load_r / load_prev / store_xv / account):
 // this wave's full rounds (both sections of a step exist: base + 2 gpw <= nsec, wave-uniform) run
 // denoise_step_grid2_full; a partial last round runs the masked step.  The same bits either way.
+// FAST == DEN_FAST_PAIR at G = 32: the full rounds run denoise_step_grid2_pair instead (the policy
+// supplies load_r2 / load_prev2 / store_xv2 / account_close); the same bits again.
 // (Requesting the next round's inputs before the current round's arithmetic was measured slower:
 // the six values held across the step spilled)
-template <bool kVar, int KK, int U, int G, bool PKG = true, bool FAST = false, class P>
+template <bool kVar, int KK, int U, int G, bool PKG = true, int FAST = DEN_FAST_NONE, class P>
 __device__ __forceinline__ bool denoise_sections_grid(const P& pol, int nsec, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block()) {
     constexpr int R = grid_r<KK>();
     if constexpr (R == 0) {
@@ -855,8 +1091,21 @@ __device__ __forceinline__ bool denoise_sections_grid(const P& pol, int nsec, co
             int base = wave * gpw * U;
             if constexpr (FAST && PKG && U == 2 && AMP_DEN_PACKED_GRID) {
                 const int step = nw * gpw * 2;
-                for (; base + 2 * gpw <= nsec; base += step)
-                    denoise_step_grid2_full<kVar, R, GRID_REF16, G>(pol, base, grid2_load<G>(pol, base), Q, pa, S);
+                if constexpr (FAST == DEN_FAST_PAIR && G == 32) {
+                    // (a wave without a full round moves its sums there and back: no branch around the loop;
+                    // the wave-uniform base as a scalar: the loop branches on SCC, not on an exec mask)
+                    base = __builtin_amdgcn_readfirstlane(base);
+                    double acc = pair_acc_in(pa.sumvar);
+                    for (; base + 2 * gpw <= nsec; base += step) {
+                        const int lane = pair_lane();   // the step's addresses formed in the step
+                        denoise_step_grid2_pair<kVar, R, GRID_REF16>(pol, base, lane, grid2_pair_load(pol, base, lane), Q, pa,
+                                                                     acc, S);
+                    }
+                    pa.sumvar = pair_acc_out(acc);
+                } else {
+                    for (; base + 2 * gpw <= nsec; base += step)
+                        denoise_step_grid2_full<kVar, R, GRID_REF16, G>(pol, base, grid2_load<G>(pol, base), Q, pa, S);
+                }
             }
             for (; base < nsec; base += nw * gpw * U) {
                 if constexpr (PKG && U == 2 && AMP_DEN_PACKED_GRID)
@@ -896,7 +1145,7 @@ __device__ __forceinline__ void denoise_sections_gp(const P& pol, int nsec, cons
 enum { PK_NONE = 0, PK_ALL = 1, PK_GRID = 2 };
 
 // Runtime M (a power of two <= 64) -> the compile-time group size.
-template <bool kVar, int KK, int U, int G, int PK, bool FAST = false, class P>
+template <bool kVar, int KK, int U, int G, int PK, int FAST = DEN_FAST_NONE, class P>
 __device__ __forceinline__ void denoise_sections_sel(const P& pol, int nsec, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block()) {
     if constexpr (PK == PK_ALL && KK % 2 == 0) {
         denoise_sections_gp<kVar, KK, U, G>(pol, nsec, c, pa, dw);
@@ -905,7 +1154,7 @@ __device__ __forceinline__ void denoise_sections_sel(const P& pol, int nsec, con
         denoise_sections_g<kVar, KK, U, G>(pol, nsec, c, pa, dw);
     }
 }
-template <bool kVar, int KK, int U, int PK = PK_ALL, bool FAST = false, class P>
+template <bool kVar, int KK, int U, int PK = PK_ALL, int FAST = DEN_FAST_NONE, class P>
 __device__ __forceinline__ void denoise_sections_u(const P& pol, int nsec, int M, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block()) {
     switch (M) {
     case 64: denoise_sections_sel<kVar, KK, U, 64, PK, FAST>(pol, nsec, c, pa, dw); break;

@@ -373,6 +373,27 @@ struct PDenoisePolicy {
         pa.sumvar += (double)var;
         pa.notclose += torch_close(var, vp) ? 0u : 1u;     // vamp.py:185
     }
+    // the same for positions m, m + 1 (m even) of one section (amp_denoise.h denoise_step_grid2_pair):
+    // one 16-byte access of r / x and one 8-byte access of the variances.  The row strides ldr and
+    // N are multiples of four floats (playout: ldr = 2N + 4 or 2N + 8; N a multiple of M >= 2;
+    // vamp_persist_launch checks it), and the row arrays start 16 bytes aligned.  A wave's four
+    // sections are 1 KB (r, x) / 512 B (var) of consecutive bytes of one row: no bank conflict.
+    __device__ __forceinline__ float4 load_r2(int sec, int m) const {
+        const int row = sec >> lspr, sj = sec & ((1 << lspr) - 1);
+        return *reinterpret_cast<const float4*>(r + row * ldr + 2 * (sj * M + m));
+    }
+    __device__ __forceinline__ float2 load_prev2(int sec, int m) const {
+        const int row = sec >> lspr, sj = sec & ((1 << lspr) - 1);
+        return *reinterpret_cast<const float2*>(vprev + row * N + sj * M + m);
+    }
+    __device__ __forceinline__ void store_xv2(int sec, int m, float4 xv, float2 var) const {
+        const int row = sec >> lspr, sj = sec & ((1 << lspr) - 1);
+        *reinterpret_cast<float4*>(x + row * ldr + 2 * (sj * M + m)) = xv;
+        *reinterpret_cast<float2*>(vnew + row * N + sj * M + m) = var;
+    }
+    __device__ __forceinline__ void account_close(float var, float vp, PartAcc& pa) const {
+        pa.notclose += torch_close(var, vp) ? 0u : 1u;     // vamp.py:185
+    }
     float* dbg = nullptr;  // diagnostic: [16][2N] ze (columns < N) and vs (columns >= N), else null
 };
 __device__ __forceinline__ void den_debug(const PDenoisePolicy& p, int sec, int m, float ze, float vs) {

@@ -148,6 +148,15 @@ static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_tm_ev;
 // launch: dc's Const64 base is overwritten with c64.
 int vamp_persist_launch(const VampK& P, const Const64& c64, const DecConst& dc, hipStream_t st, int ncu) {
     (void)ncu;
+    if (P.x3) {
+        // the position-pair denoiser step moves 16 bytes of r / x and 8 of the variances per lane
+        // (PDenoisePolicy load_r2 / store_xv2): row strides and carve offsets in whole float4
+        const PLayout y = playout(P.N, P.k, P.L, true);
+        if ((y.ldr | P.N | y.offR | y.offX | y.offV0 | y.offV1) % 4 != 0) {
+            set_error("vamp_persist: LDS rows not 16-byte aligned (N = %d, ldr = %d)", P.N, y.ldr);
+            return AMP_E_ARG;
+        }
+    }
     DecConst d2 = dc;
     static_cast<Const64&>(d2) = c64;
     hipEvent_t te[2] = {nullptr, nullptr};

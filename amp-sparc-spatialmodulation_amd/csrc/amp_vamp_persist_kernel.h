@@ -33,6 +33,9 @@ constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iter
 #ifndef AMP_X3_W8_DENFAST
 #define AMP_X3_W8_DENFAST 1             // the eight-wave form's full-round packed denoiser step (A/B builds: 0)
 #endif
+#ifndef AMP_X3_W8_DENPAIR
+#define AMP_X3_W8_DENPAIR 1             // at M = 32 that step takes two positions of one section per lane (A/B builds: 0)
+#endif
 #ifndef AMP_DECIDE_NARROW
 #define AMP_DECIDE_NARROW 1             // the epilogue's narrowed candidate scan at one workgroup per CU (A/B builds: 0)
 #endif
@@ -114,7 +117,9 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                           : (NWV == 8 && KK == 16 && AMP_X3_W8_PKGRID) ? PK_GRID : PK_NONE;
     // the eight-wave form at one workgroup per CU: the packed grid step's full rounds with no masking
     // and no control flow between their loads and stores (amp_denoise.h denoise_sections_grid FAST)
-    constexpr bool DENFAST = NWV == 8 && OCC == 1 && PKDEN == PK_GRID && AMP_X3_W8_DENFAST;
+    // (at M = 32 its position-pair form, denoise_step_grid2_pair)
+    constexpr int DENFAST = !(NWV == 8 && OCC == 1 && PKDEN == PK_GRID && AMP_X3_W8_DENFAST) ? DEN_FAST_NONE
+                            : AMP_X3_W8_DENPAIR ? DEN_FAST_PAIR : DEN_FAST_FULL;
     constexpr int PWG = 64 * NWV;
     constexpr int NC = X3 ? NT / 2 : 1;        // complex column tiles per wave (X3)
     constexpr int G3 = NT * NWV / 4;           // 32-wide complex reduction groups: N / 32

@@ -3,13 +3,17 @@
 tests/test_gpu_vamp_ring_prefill.py (tests/golden/ring_prefill_bits.part<k>.npz).
 
   python tools/record_forward_bits.py [--out DIR] [--stem STEM] [--cases "Nt,Na,Nr,B,alphabet;..."] [--share-channel]
-                                      [--ebn0 "dB;..."]
+                                      [--ebn0 "dB;..."] [--nan-row "row;..."] [--dump]
 
 --stem / --cases record another fixture (tests/golden/<stem>.part<k>.npz) for another case list;
 --share-channel draws one channel, the first case's, stores it once ('shared/U', 's', 'Vh', 'SNR')
 and runs every case that agrees with it in Nt and Nr on it (another case draws and stores its own);
 --ebn0 sets Eb/N0 per case (one value: every case; an empty entry: the alphabet's default) and
-stores that case's SNR as '<case>/SNR', e.g. to record a forward that stops before the cap.
+stores that case's SNR as '<case>/SNR', e.g. to record a forward that stops before the cap;
+--nan-row sets one row of y to NaN per case (an empty entry: none), in both forwards;
+--dump runs the reuse forward with the persistent engine's per-iteration state dump on and stores,
+for the iterations it ran, every valid trial's var ('f1_it_var'), each wave's float64 var sum
+('f1_it_wsum') and the exchange records the workgroups published ('f1_it_gran').
 
 Public API only (Config, Channel, Data, VAMP, amp_native.prepare_counts), so the same script runs
 on any commit: a change that must leave the engine's results bit-identical is checked against a
@@ -48,10 +52,11 @@ def config(Nt, Na, Nr, B, alphabet, device):
                   channel_profile='uniform', channel_truncation='tail', device=device)
 
 
-def make_inputs(case, shared=None, ebn0=None):
+def make_inputs(case, shared=None, ebn0=None, nan_row=None):
     """One channel and two epochs of messages + noise (host tensors), in the reference's call order.
     shared: the make_inputs result of another case whose channel (A, U, s, Vh, SNR) this one uses;
-    ebn0: this case's own Eb/N0 (else the alphabet's default, or the shared channel's SNR)."""
+    ebn0: this case's own Eb/N0 (else the alphabet's default, or the shared channel's SNR);
+    nan_row: the row of y set to NaN in both epochs."""
     from channel import Channel
     from data import Data
     np.random.seed(SEED)
@@ -69,7 +74,10 @@ def make_inputs(case, shared=None, ebn0=None):
     eps = []
     for _ in range(2):
         x, sym, idx = da.generate_message()
-        eps.append(dict(x=x, sym=sym, idx=idx, y=A @ x + ch.awgn(SNR)))
+        y = A @ x + ch.awgn(SNR)
+        if nan_row is not None:
+            y[nan_row] = float('nan')
+        eps.append(dict(x=x, sym=sym, idx=idx, y=y))
     return dict(A=A, U=U, s=s, Vh=Vh, SNR=SNR, eps=eps)
 
 
@@ -89,12 +97,52 @@ def forward(det, chan, SNR, ep, device):
     return (b1 - b0, r1 - r0), out
 
 
-def run_case(case, inp, device):
-    """A building forward, then a reuse forward with a new y on the same channel objects."""
+PBM = 16     # trials per persistent workgroup (csrc/amp_vamp.h)
+ITERS = 20   # config()'s iteration cap
+
+
+def dumped_forward(det, cfg, chan, SNR, ep, device):
+    """forward() with the persistent engine's state dump on (amp_vamp_debug_dump); adds, for the
+    iterations that ran: it_var [T, B, N] float32, it_wsum [T, nwg, waves] float64 (each wave's var
+    sum), it_gran [T, nwg, 8] uint32 (the exchange records: sumvar, notclose, tag, max|xi|, min max, 0, tag)."""
+    import ctypes as C
+    import amp_native as nat
+    B, N = cfg.B, cfg.dims().N
+    nwg = -(-B // PBM)
+    dump = torch.zeros(ITERS, nwg, 5, PBM, 2 * N, dtype=torch.float32, device=device)
+    nat.check(nat.lib().amp_vamp_debug_dump(C.c_void_p(dump.data_ptr())), 'amp_vamp_debug_dump')
+    try:
+        made, out = forward(det, chan, SNR, ep, device)
+        torch.cuda.synchronize()
+    finally:
+        nat.lib().amp_vamp_debug_dump(None)
+    T = int(out['T'][0])
+    assert int(det.last.status().gemm) == 2, 'the dump is the persistent bf16x3 engine\'s'
+    d = dump.cpu().numpy()
+    off = (C.c_uint64 * 5)()
+    nat.check(nat.lib().amp_vamp_debug_offsets(C.byref(cfg.dims()), N, ITERS, 1, off), 'amp_vamp_debug_offsets')
+    gran = det.last.buf.ws[int(off[0]):int(off[0]) + ITERS * nwg * 32].cpu().numpy().view(np.uint32).reshape(ITERS, nwg, 8)
+    rows = [min(PBM, B - w * PBM) for w in range(nwg)]
+    waves = 8 if N >= 256 else 4
+    out['it_var'] = np.concatenate([d[:T, w, 3, :rows[w], :N] for w in range(nwg)], axis=1).copy()
+    out['it_wsum'] = np.ascontiguousarray(d[:T, :, 3, 0, N:N + 2 * waves]).view(np.float64).copy()
+    out['it_gran'] = gran[:T].copy()
+    return made, out
+
+
+def run_case(case, inp, device, dump=False):
+    """A building forward, then a reuse forward with a new y on the same channel objects
+    (dump: the reuse forward with the state dump on)."""
     from vamp import VAMP
-    det = VAMP(config(*case, device='cuda'))
+    cfg = config(*case, device='cuda')
+    det = VAMP(cfg)
     chan = tuple(inp[k].to(device).contiguous() for k in ('U', 's', 'Vh'))
-    return [forward(det, chan, inp['SNR'], ep, device) for ep in inp['eps']]
+    res = [forward(det, chan, inp['SNR'], inp['eps'][0], device)]
+    if dump:
+        res.append(dumped_forward(det, cfg, chan, inp['SNR'], inp['eps'][1], device))
+    else:
+        res.append(forward(det, chan, inp['SNR'], inp['eps'][1], device))
+    return res
 
 
 def as_np(v):
@@ -141,6 +189,8 @@ def main():
     ap.add_argument('--share-channel', action='store_true',
                     help="one channel, the first case's, stored once and used by every case")
     ap.add_argument('--ebn0', default=None, help='"dB;..." per case (one value: every case; empty: the default)')
+    ap.add_argument('--nan-row', default=None, help='"row;..." per case: that row of y is NaN (empty: none)')
+    ap.add_argument('--dump', action='store_true', help="the reuse forward's per-iteration var, wave sums and exchange records")
     args = ap.parse_args()
     cases = CASES if args.cases is None else [
         tuple(int(v) for v in c.split(',')[:4]) + (c.split(',')[4],) for c in args.cases.split(';')]
@@ -150,14 +200,19 @@ def main():
         vals = vals * len(cases) if len(vals) == 1 else vals
         assert len(vals) == len(cases), (vals, cases)
         ebn0 = [float(v) if v.strip() else None for v in vals]
+    nan_rows = [None] * len(cases)
+    if args.nan_row is not None:
+        vals = args.nan_row.split(';')
+        assert len(vals) == len(cases), (vals, cases)
+        nan_rows = [int(v) if v.strip() else None for v in vals]
     device = torch.device('cuda', 0)
     flat = {}
     shared = None
-    for case, eb in zip(cases, ebn0):
+    for case, eb, nr in zip(cases, ebn0, nan_rows):
         name = case_name(*case)
         own = shared is not None and case[0:3:2] != shared['dims']   # another Nt, Nr: its own channel
-        inp = make_inputs(case, None if own else shared, eb)
-        res = run_case(case, inp, device)
+        inp = make_inputs(case, None if own else shared, eb, nr)
+        res = run_case(case, inp, device, args.dump)
         print(name, 'prepares (building, reuse) per forward:', [m for m, _ in res],
               'T:', [int(o['T'][0]) for _, o in res])
         if args.share_channel and shared is None:

@@ -13,7 +13,7 @@
 
 using namespace amp;
 
-template <int KK, int U, int NWV, int PK, bool FAST = false>
+template <int KK, int U, int NWV, int PK, int FAST = 0>
 __global__ __launch_bounds__(64 * NWV, 1) void ub(const float* rin, Const c, int N, int M, float inv, int reps,
                                                 unsigned long long* out, double* sink) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void ub(const float* rin, Const c, int
     if ((threadIdx.x & 63) == 0) sink[blockIdx.x * NWV + (threadIdx.x >> 6)] = pa.sumvar + pa.notclose;
 }
 
-template <int KK, int U, int NWV, int PK, bool FAST = false>
+template <int KK, int U, int NWV, int PK, int FAST = 0>
 static void run(const char* tag, const float* dr, const Const& c, int N, int M, float inv, unsigned long long* dout,
                 double* dsink) {
     const int nwg = 256, reps = 20;
@@ -107,7 +107,9 @@ extern "C" int ubench_main() {
     run<16, 1, 16, false>("cfg4 16QAM grid", dr, c, N, M, inv, dout, dsink);
     // vamp_persist's eight-wave form (PK_GRID): the masked packed step, then its full-round form
     run<16, 2, 8, PK_GRID, false>("cfg4 16QAM packed grid", dr, c, N, M, inv, dout, dsink);
-    run<16, 2, 8, PK_GRID, true>("cfg4 16QAM packed grid", dr, c, N, M, inv, dout, dsink);
+    run<16, 2, 8, PK_GRID, DEN_FAST_FULL>("cfg4 16QAM packed grid", dr, c, N, M, inv, dout, dsink);
+    // and its position-pair form at M = 32 (two positions of one section per lane)
+    run<16, 2, 8, PK_GRID, DEN_FAST_PAIR>("cfg4 16QAM packed grid pair", dr, c, N, M, inv, dout, dsink);
     fflush(stdout);
     return 0;
 }
