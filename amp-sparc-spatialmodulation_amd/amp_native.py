@@ -151,6 +151,12 @@ SIGNATURES = {
     'amp_bamp_trials_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _P]),
     'amp_scamp_trials_workspace_bytes': (C.c_size_t, [_D, _I, _I]),
     'amp_scamp_trials_run': (C.c_int, [_D, _K, C.POINTER(AmpScampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _P]),
+    # several channels per trial batch: trial e uses channel e // per_channel
+    'amp_bamp_trials_ch_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I]),
+    'amp_bamp_trials_ch_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _I, _P]),
+    'amp_scamp_trials_ch_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I]),
+    'amp_scamp_trials_ch_run': (C.c_int, [_D, _K, C.POINTER(AmpScampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _I,
+                                          _P]),
     'amp_bamp_workspace_bytes': (C.c_size_t, [_D, _I]),
     'amp_bamp_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),
     'amp_bamp_prepare': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),

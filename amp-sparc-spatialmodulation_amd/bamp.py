@@ -23,7 +23,7 @@ from torch import nn
 import amp_native as nat
 from config import Config
 from loss import Loss
-from vamp import LazyResult, ShardHook, _c64, block_denoise
+from vamp import LazyResult, ShardHook, _c64, _channel_stack, block_denoise
 
 
 class _Buffers:
@@ -196,7 +196,14 @@ class BAMP(LazyResult, nn.Module):
         self.last = T
         return self.L
 
-    def forward_trials(self, H: torch.Tensor, ys, SNR: float, xs, symbols, indices) -> list:
+    def trials_workspace_bytes(self, trials: int, per_channel: int) -> int:
+        """Workspace bytes of a forward_trials call of `trials` trials at `per_channel` per channel
+        (amp_bamp_trials_ch_workspace_bytes; 0: the call would be refused)."""
+        d = self.config.dims()
+        return int(nat.lib().amp_bamp_trials_ch_workspace_bytes(C.byref(d), self.config.N_Layers, int(trials),
+                                                                int(per_channel)))
+
+    def forward_trials(self, H, ys, SNR: float, xs, symbols, indices, per_channel: int | None = None) -> list:
         """E independent single-trial detections that share ONE channel H and one SNR, in one
         launch sequence (amp_bamp_trials_run) — the epochs of one `res` block of the reference's
         drivers, which run batch = 1 (bamp_model.py:89, 96).  Each trial is the B = 1 forward of
@@ -204,17 +211,31 @@ class BAMP(LazyResult, nn.Module):
         count (bamp.py:140), decided and counted as Loss at B = 1 in generator_mode 'sparc' or
         'segmented'.  Returns E Loss objects (in order) that equal E sequential forward() calls;
         they resolve lazily.  ys / xs / symbols / indices as VAMP.forward_trials.
-        ValueError unless config.B == 1."""
+        ValueError unless config.B == 1.
+        Several channels (amp_bamp_trials_ch_run): H a list of G matrices or one [G, n, N] tensor
+        together with per_channel = R; trial e then uses channel e // R (the last channel may hold
+        fewer than R trials; R = 1 is a channel per trial), and each trial still equals its own
+        forward() with its own channel.  ValueError unless G == ceil(E / R).  A single matrix
+        without per_channel is the one-channel call."""
         E = self._trials_check(ys, xs, symbols, indices)
+        multi = per_channel is not None or isinstance(H, (list, tuple))
+        if multi:
+            Hc, R, n, N = _channel_stack(H, E, per_channel, 'H')
         dev = ys[0].device
         with torch.cuda.device(dev):
             cfg = self.config
-            n, N = H.shape[-2], H.shape[-1]
-            Hc = _c64(H, (n, N))
+            if multi:
+                Hc = Hc.to(dev)
+            else:
+                n, N = H.shape[-2], H.shape[-1]
+                Hc = _c64(H, (n, N))
             y, x, sym, idx, res, host, dec = self._trials_inputs(ys, xs, symbols, indices, E, n, dev)
             d, cst = cfg.dims(), cfg.constellation()
             lib = nat.lib()
-            wsb = lib.amp_bamp_trials_workspace_bytes(C.byref(d), cfg.N_Layers, E)
+            if multi:
+                wsb = lib.amp_bamp_trials_ch_workspace_bytes(C.byref(d), cfg.N_Layers, E, R)
+            else:
+                wsb = lib.amp_bamp_trials_workspace_bytes(C.byref(d), cfg.N_Layers, E)
             if wsb == 0:
                 raise ValueError('amp_bamp_trials_workspace_bytes: invalid dimensions')
             ws = nat.WORKSPACE.get(dev, 'bamp_trials', wsb)
@@ -231,8 +252,12 @@ class BAMP(LazyResult, nn.Module):
             a.xmap, a.xmmse, a.var = nat.dptr(xmap), nat.dptr(xm), nat.dptr(var)
             a.status = nat.dptr(res)
             a.ws, a.ws_bytes = nat.dptr(ws), ws.numel()
-            nat.check(lib.amp_bamp_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
-                                              nat.stream_ptr(dev)), 'amp_bamp_trials_run')
+            if multi:
+                nat.check(lib.amp_bamp_trials_ch_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E, R,
+                                                     nat.stream_ptr(dev)), 'amp_bamp_trials_ch_run')
+            else:
+                nat.check(lib.amp_bamp_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
+                                                  nat.stream_ptr(dev)), 'amp_bamp_trials_run')
             out = self._trials_losses(res, host, E, dev)
             self._trials_keep = (y, x, sym, idx, Hc)   # alive until the kernels have read them
             self.last_trials = (xmap.view(E, 1, N, 1), xm.view(E, 1, N, 1), var.view(E, 1, N, 1))

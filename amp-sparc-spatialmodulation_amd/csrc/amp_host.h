@@ -289,6 +289,18 @@ int build_abs2_weight(const float2* src, long so, long sj, int O, int J, float* 
 // the tile is all zero).  One pass over the weight (amp_weights.hip).
 int weight_kband(const float* wp, int kap, int ncp, int BN, int* band, hipStream_t st);
 int h2_kband(const void* wq, int PL, int G, int tpt, int ntiles, int n16, int* band, hipStream_t st);
+// build_cweight (WPACK32, no row scale), build_abs2_weight and weight_kband for `nch` channels in one
+// launch each (three for the band ranges), the channel on a grid axis: channel g's source at
+// src + g * sg (float2 elements), its packed operator at wt + g * dg (floats), its band ranges at
+// band + g * bstride (ints; bstride even, >= 2 ncp / BN).  A channel's operator and ranges have the
+// bits of the single-channel calls on that channel alone.
+constexpr int WCH_MAX = 65535;   // channels per call: a grid axis
+int build_cweight_ch(const float2* src, size_t sg, long so, long sj, int conj, int O, int J, float* wt, size_t dg,
+                     int kap, int ncp, int nch, hipStream_t st);
+int build_abs2_weight_ch(const float2* src, size_t sg, long so, long sj, int O, int J, float* wt, size_t dg, int kap,
+                         int ncp, int nch, hipStream_t st);
+int weight_kband_ch(const float* wp, size_t dg, int kap, int ncp, int BN, int* band, int bstride, int nch,
+                    hipStream_t st);
 
 // Grid of the launch engines' rare-path fix-up launches (grid-stride over `work` sections, one
 // count slot per workgroup within the iteration's nblk partial slots): at most two workgroups per

@@ -15,6 +15,9 @@
 // settles its exit or leaves a pending exact float64 fix-up in the trial's record, which
 // tscamp_fix_sec and tscamp_fix_psi_fin (also grids over the trials) carry out against the trial's
 // own max|xi|.  Every kernel returns at once when the stop counter has reached E.
+// amp_scamp_trials_ch_run: the same over G channels, trial e on channel e / per_channel: the channel
+// forms of the two GEMM kernels (tscamp_ka_ch, tscamp_kb_ch) and the operators of all channels
+// packed in a number of launches that does not depend on G; every other kernel as it is.
 #include <algorithm>
 #include <mutex>
 
@@ -41,13 +44,15 @@ struct TScampWs {
     size_t bytes;
 };
 
-static TScampWs tscamp_carve(const amp_dims* d, int E, void* base) {
+// G: channels whose packed operators and band ranges the workspace holds (amp_scamp_trials_ch_run;
+// one channel: the layout and bytes of amp_scamp_trials_run)
+static TScampWs tscamp_carve(const amp_dims* d, int E, void* base, int G = 1) {
     ScampK P;
     scamp_geometry(d, E, P);
     Carve cv(base);
     TScampWs w;
-    w.WA = cv.take<float>((size_t)P.ncpA * P.kapA);
-    w.WAH = cv.take<float>((size_t)P.ncpB * P.kapB);
+    w.WA = cv.take<float>((size_t)G * P.ncpA * P.kapA);
+    w.WAH = cv.take<float>((size_t)G * P.ncpB * P.kapB);
     w.z = cv.take<float>((size_t)E * 2 * d->n);
     w.s = cv.take<float>((size_t)E * scamp_sld(d->n));
     w.phi = cv.take<float>((size_t)2 * E * d->Lout);
@@ -59,8 +64,8 @@ static TScampWs tscamp_carve(const amp_dims* d, int E, void* base) {
     w.psi_nc = cv.take<unsigned>((size_t)E * d->Lin);
     w.fixcnt = cv.take<int>((size_t)E);
     w.iters = cv.take<ScampIter>((size_t)E);
-    w.bandA = cv.take<int>((size_t)2 * (P.ncpA / 128));
-    w.bandB = cv.take<int>((size_t)2 * (P.ncpB / P.bn));
+    w.bandA = cv.take<int>(G == 1 ? (size_t)2 * (P.ncpA / 128) : (size_t)G * band_stride(P.ncpA / 128));
+    w.bandB = cv.take<int>(G == 1 ? (size_t)2 * (P.ncpB / P.bn) : (size_t)G * band_stride(P.ncpB / P.bn));
     w.nstop = cv.take<unsigned>(16);
     w.dec = cv.take<char>(trials_decide_ws_bytes(d, E));
     w.bytes = cv.off;
@@ -103,6 +108,60 @@ __global__ __launch_bounds__(AMP_WG) void tscamp_kb(ScampK P, ScampTrials R, int
     const int kb = P.bandB ? P.bandB[2 * tile.cb] : 0, ke = P.bandB ? P.bandB[2 * tile.cb + 1] : -1;
     gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, sld, P.B, sld}, P.WAH, P.kapB, row0, col0, lds, kb, ke);
     const int nrows = min(GBM, P.B - row0), ncols = min(BN, 2 * P.N - col0);
+    const ScampTileBlocks tb = scamp_tile_blocks(P, col0, ncols);
+    const float* tau_t = scamp_xmap<BN, KC>(P, LiveRows{s_stop}, t, lds, row0, col0, nrows, ncols, tb);
+    const int nct = P.ncpB / BN, slot = seq_part_slot(tile.cb, nct);
+    for (int rho = 0; rho < nrows; ++rho) {
+        if (s_stop[rho]) continue;   // workgroup-uniform
+        const ScampDenoisePolicy pol = scamp_policy<BN, KC>(P, lds, tau_t, row0, col0, ncols, tb, rho);
+        PartAcc pa;
+        denoise_sections<false, KK>(pol, pol.spr, P.M, P.c, pa);
+        __syncthreads();
+        if (!P.psi_split && (int)threadIdx.x < tb.nlc)
+            pa.notclose += scamp_psi_in_tile(P, t, row0 + rho, tb.lc0 + threadIdx.x);
+        part_block_store(pa, P.parts + (size_t)(row0 + rho) * nct + slot, lds + C::CTILE_FLOATS);
+    }
+}
+
+// ---- the channel forms of the two GEMM kernels (amp_scamp_trials_ch_run): row tile rb belongs to
+// channel rb / tpg (amp_trials.h channel_tile).  The kernel takes the channel's view of the
+// parameter block at its entry (its operators and band ranges), stages and guards its rows up to
+// the channel's limit, and runs the same gemm_tile call and epilogue: a row has the bits of its own
+// B = 1 forward with that channel, wherever in a tile it lies.  The stop counter is still compared
+// with E (P.B), and every other kernel of the iteration is per trial and runs as it is. ----
+
+__global__ __launch_bounds__(AMP_WG) void tscamp_ka_ch(ScampK P, ScampTrials R, TrialChannels CH, int t) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ int s_stop[GBM];
+    const GemmTile tile = xcd_tile();
+    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const int row0 = ct.row0, col0 = tile.cb * 128;
+    if (*R.nstop >= (unsigned)P.B) return;
+    if (!tile_rows_live(P.iters, row0, ct.lim, s_stop)) return;
+    P.WA += (size_t)ct.g * CH.wstride[0];
+    if (P.bandA) P.bandA += (size_t)ct.g * CH.bstride[0];
+    const int twoN = 2 * P.N;
+    const int kb = P.bandA ? P.bandA[2 * tile.cb] : 0, ke = P.bandA ? P.bandA[2 * tile.cb + 1] : -1;
+    gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.xm, twoN, ct.lim, twoN}, P.WA, P.kapA, row0, col0, lds, kb, ke);
+    scamp_residual<256>(P, LiveRows{s_stop}, t, lds, row0, col0);
+}
+
+template <int BN, int KK, int KC>
+__global__ __launch_bounds__(AMP_WG) void tscamp_kb_ch(ScampK P, ScampTrials R, TrialChannels CH, int t) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ int s_stop[GBM];
+    using C = GemmCfg<BN, KC>;
+    const GemmTile tile = xcd_tile();
+    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const int row0 = ct.row0, col0 = tile.cb * BN;
+    if (*R.nstop >= (unsigned)P.B) return;
+    if (!tile_rows_live(P.iters, row0, ct.lim, s_stop)) return;
+    P.WAH += (size_t)ct.g * CH.wstride[1];
+    if (P.bandB) P.bandB += (size_t)ct.g * CH.bstride[1];
+    const int sld = scamp_sld(P.n);
+    const int kb = P.bandB ? P.bandB[2 * tile.cb] : 0, ke = P.bandB ? P.bandB[2 * tile.cb + 1] : -1;
+    gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, sld, ct.lim, sld}, P.WAH, P.kapB, row0, col0, lds, kb, ke);
+    const int nrows = min(GBM, ct.lim - row0), ncols = min(BN, 2 * P.N - col0);
     const ScampTileBlocks tb = scamp_tile_blocks(P, col0, ncols);
     const float* tau_t = scamp_xmap<BN, KC>(P, LiveRows{s_stop}, t, lds, row0, col0, nrows, ncols, tb);
     const int nct = P.ncpB / BN, slot = seq_part_slot(tile.cb, nct);
@@ -267,6 +326,41 @@ static void tscamp_launch_kb(const ScampK& P, const ScampTrials& R, int gr, int 
         hipLaunchKernelGGL((tscamp_kb<256, KK, GKC>), dim3(gr, P.ncpB / 256), dim3(AMP_WG), TS_LDS_W, st, P, R, t);
 }
 
+static std::once_flag g_tscamp_ch_once;
+static int g_tscamp_ch_rc = 0;
+static int tscamp_ch_attrs() {
+    std::call_once(g_tscamp_ch_once, [] {
+        for (int K : {1, 2, 4, 8, 16, 64})
+            dispatch_K(K, [](auto kk) {
+                if (!g_tscamp_ch_rc)
+                    g_tscamp_ch_rc = set_lds_attr<256>((const void*)tscamp_kb_ch<256, decltype(kk)::value, GKC>);
+            });
+    });
+    return g_tscamp_ch_rc;
+}
+
+template <int KK>
+static void tscamp_launch_kb_ch(const ScampK& P, const ScampTrials& R, const TrialChannels& CH, int gr, int t,
+                                hipStream_t st) {
+    if (P.bn == 128)
+        hipLaunchKernelGGL((tscamp_kb_ch<128, KK, 256>), dim3(gr, P.ncpB / 128), dim3(AMP_WG), TS_LDS_S, st, P, R, CH, t);
+    else
+        hipLaunchKernelGGL((tscamp_kb_ch<256, KK, GKC>), dim3(gr, P.ncpB / 256), dim3(AMP_WG), TS_LDS_W, st, P, R, CH, t);
+}
+
+// The operators of G channels (A: c64 [G][n][N]) and their band ranges, each channel's own, in a
+// number of launches that does not depend on G: 2 builds + 2 x 3 for the ranges
+static int tscamp_pack_ch(const ScampK& P, const TrialChannels& CH, const float2* A, int G, hipStream_t st) {
+    int rc;
+    const size_t sg = (size_t)P.n * P.N;
+    if ((rc = build_cweight_ch(A, sg, P.N, 1, 0, P.n, P.N, (float*)P.WA, CH.wstride[0], P.kapA, P.ncpA, G, st))) return rc;
+    if ((rc = build_cweight_ch(A, sg, 1, P.N, 1, P.N, P.n, (float*)P.WAH, CH.wstride[1], P.kapB, P.ncpB, G, st))) return rc;
+    if (!P.bandA) return AMP_OK;
+    if ((rc = weight_kband_ch(P.WA, CH.wstride[0], P.kapA, P.ncpA, 128, const_cast<int*>(P.bandA), CH.bstride[0], G, st)))
+        return rc;
+    return weight_kband_ch(P.WAH, CH.wstride[1], P.kapB, P.ncpB, P.bn, const_cast<int*>(P.bandB), CH.bstride[1], G, st);
+}
+
 // any Nt (amp_scamp_run's shapes); the byte query answers 0 for dims the run would refuse
 static bool tscamp_shape_ok(const amp_dims* d, int E) {
     return d->Nt > 0 && d->Na > 0 && d->Nr > 0 && d->Lin > 0 && d->Lout > 0 && d->Lin <= SMAXLIN &&
@@ -338,6 +432,83 @@ int amp_scamp_trials_run(const amp_dims* d, const amp_constellation* c, const am
         hipLaunchKernelGGL(tscamp_fix_sec, dim3(E), dim3(TSRWG), 0, st, P, R, c64, t);
         hipLaunchKernelGGL(tscamp_fix_psi_fin, dim3(E), dim3(TSRWG), 0, st, P, R, t);
         AMP_LAUNCH_CHECK("tscamp iteration");
+    }
+    hipLaunchKernelGGL(tscamp_output_kernel, dim3(E), dim3(64), 0, st, P);
+    AMP_LAUNCH_CHECK("tscamp_output");
+    return dec ? trials_decide_launch(d, c, td, E, w.dec, st) : AMP_OK;
+}
+
+size_t amp_scamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel) {
+    if (!d || max_iter <= 0 || trials <= 0 || per_channel < 1 || d->B != 1 || !tscamp_shape_ok(d, trials)) return 0;
+    int per = per_channel;
+    const int G = trial_channels(trials, per);
+    if (G > WCH_MAX) return 0;
+    return tscamp_carve(d, trials, nullptr, G).bytes;
+}
+
+int amp_scamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
+                            const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
+    int rc = check_dims(d, c, true, true);   // any Nt, a partial last column tile (amp_scamp_run)
+    if (rc) return rc;
+    AMP_REQUIRE(d->B == 1, "amp_scamp_trials_ch_run: dims describe ONE trial (B = %d, must be 1)", d->B);
+    AMP_REQUIRE(trials >= 1, "amp_scamp_trials_ch_run: trials = %d", trials);
+    AMP_REQUIRE(per_channel >= 1, "amp_scamp_trials_ch_run: per_channel = %d", per_channel);
+    AMP_REQUIRE(a && a->W && a->A && a->y && a->xmap && a->xmmse && a->psi && a->status && a->ws,
+                "amp_scamp_trials_ch_run: null pointer argument");
+    AMP_REQUIRE(a->max_iter > 0, "amp_scamp_trials_ch_run: max_iter must be positive");
+    AMP_REQUIRE(d->Lin <= SMAXLIN, "amp_scamp_trials_ch_run: Lin = %d > %d", d->Lin, SMAXLIN);
+    AMP_REQUIRE(scamp_index_ok(d, trials), "amp_scamp_trials_ch_run: %d trials of max(2N, 2n) = %d columns need more "
+                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
+    AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES,
+                "amp_scamp_trials_ch_run: launch engine only (engine %d)", a->engine);
+    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "amp_scamp_trials_ch_run: f32 GEMMs only (gemm %d)",
+                a->gemm);
+    const int E = trials;
+    int per = per_channel;
+    const int G = trial_channels(E, per);
+    AMP_REQUIRE(G <= WCH_MAX, "amp_scamp_trials_ch_run: %d channels (at most %d per call: a grid axis)", G, WCH_MAX);
+    const TScampWs w = tscamp_carve(d, E, a->ws, G);
+    AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_scamp_trials_ch_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
+    TrialsDecide td{};
+    if (dec && (rc = trials_decide_args(d, dec, a->xmap, a->xmmse, td))) return rc;
+    if ((rc = tscamp_ch_attrs())) return rc;
+    ScampK P{};            // f32 tiles (lx3 = 0); the persistent engine's fields stay null
+    scamp_geometry(d, E, P);
+    P.max_iter = a->max_iter;
+    P.sigma2 = (float)a->noise_var;
+    P.W = (const float*)a->W;          // ONE W: channel.py:80-83 builds it from the config alone
+    P.WA = w.WA; P.WAH = w.WAH;        // channel 0's; the GEMM kernels step to their channel's
+    P.y = (const float*)a->y; P.z = w.z; P.s = w.s; P.phi = w.phi; P.tau = w.tau;
+    P.xmap = (float*)a->xmap; P.xm = (float*)a->xmmse; P.psi0 = (float*)a->psi; P.psi1 = w.psi1;
+    P.secmax = w.secmax; P.secabs = w.secabs; P.parts = w.parts;
+    P.iters = w.iters;
+    P.status = (amp_status*)a->status;
+    const bool band = d->Lin > 1 || d->Lout > 1;   // block-banded A (channel.py:75-95)
+    P.bandA = band ? w.bandA : nullptr;
+    P.bandB = band ? w.bandB : nullptr;
+    P.c = to_const(c);
+    TrialChannels CH{};
+    CH.per = per; CH.tpg = cdiv(per, GBM);
+    CH.wstride[0] = (size_t)P.ncpA * P.kapA; CH.wstride[1] = (size_t)P.ncpB * P.kapB;
+    CH.bstride[0] = G == 1 ? 2 * (P.ncpA / 128) : band_stride(P.ncpA / 128);
+    CH.bstride[1] = G == 1 ? 2 * (P.ncpB / P.bn) : band_stride(P.ncpB / P.bn);
+    const ScampTrials R{w.nstop, w.fixcnt, w.psi_nc};
+    const Const64 c64 = to_const64(c);
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = tscamp_pack_ch(P, CH, (const float2*)a->A, G, st))) return rc;   // every channel's operators, once per call
+    const size_t tot = std::max(std::max((size_t)E * P.N, (size_t)E * P.n), (size_t)E * std::max(P.Lout, P.Lin));
+    hipLaunchKernelGGL(tscamp_init_kernel, dim3((int)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, P, R);
+    AMP_LAUNCH_CHECK("tscamp_init");
+    const int gr = G * CH.tpg;                     // <= E row tiles
+    const int npsi = std::max(1, std::min(cdiv(E * P.Lin, AMP_WG / 64), 2048));
+    for (int t = 0; t < P.max_iter; ++t) {
+        hipLaunchKernelGGL(tscamp_ka_ch, dim3(gr, P.ncpA / 128), dim3(AMP_WG), TS_LDS_S, st, P, R, CH, t);
+        dispatch_K(P.c.K, [&](auto kk) { tscamp_launch_kb_ch<decltype(kk)::value>(P, R, CH, gr, t, st); });
+        if (P.psi_split) hipLaunchKernelGGL(tscamp_psi, dim3(npsi), dim3(AMP_WG), 0, st, P, R, t);
+        hipLaunchKernelGGL(tscamp_r, dim3(E), dim3(TSRWG), 0, st, P, R, c64, t);
+        hipLaunchKernelGGL(tscamp_fix_sec, dim3(E), dim3(TSRWG), 0, st, P, R, c64, t);
+        hipLaunchKernelGGL(tscamp_fix_psi_fin, dim3(E), dim3(TSRWG), 0, st, P, R, t);
+        AMP_LAUNCH_CHECK("tscamp_ch iteration");
     }
     hipLaunchKernelGGL(tscamp_output_kernel, dim3(E), dim3(64), 0, st, P);
     AMP_LAUNCH_CHECK("tscamp_output");

@@ -46,6 +46,36 @@ __device__ __forceinline__ bool tile_rows_live(const REC* recs, int row0, int ro
     return live != 0;
 }
 
+// Several channels per trial batch (amp_bamp_trials_ch_run / amp_scamp_trials_ch_run): trial e uses
+// channel e / per, so channel g owns rows [g per, min((g + 1) per, E)) and tpg = ceil(per / 32) row
+// tiles of the grid; row tile rb belongs to channel rb / tpg and starts at row g per + (rb % tpg) 32
+// (no multiple of 32 in general, and possibly odd).  `lim`, the channel's last row + 1, is the row
+// limit of the tile's A loader and of tile_rows_live: rows of the next channel that fall inside the
+// 32-row tile are staged as zeros and marked stopped, so they are neither multiplied with this
+// channel's operator nor stored.  wstride / bstride: floats / ints between two channels' packed
+// operators / band ranges (per GEMM operator of the engine).
+struct TrialChannels {
+    int per, tpg;
+    size_t wstride[4];
+    int bstride[4];
+};
+struct ChannelTile {
+    int g, row0, lim;
+};
+__device__ __forceinline__ ChannelTile channel_tile(const TrialChannels& C, int rb, int E) {
+    const int g = rb / C.tpg;
+    return ChannelTile{g, g * C.per + (rb - g * C.tpg) * GBM, min((g + 1) * C.per, E)};
+}
+// ints between two channels' band ranges of an operator with `ntiles` column tiles: whole 256-byte
+// workspace granules, so G channels cost exactly G times one channel's bytes
+inline int band_stride(int ntiles) { return (2 * ntiles + 63) & ~63; }
+// channels of `trials` trials at `per` per channel (both >= 1); per is clamped to the trials, so one
+// channel takes exactly the single-channel grid
+inline int trial_channels(int trials, int& per) {
+    per = per < trials ? per : trials;
+    return (trials + per - 1) / per;
+}
+
 // The row guard of a GEMM epilogue that the launch engine and the independent-trial engine share
 // (amp_bamp.h, amp_scamp.h): which rows of the tile it may store to.  The batch engine stores every
 // row (live() is a constant, the test folds away); the trial engine never stores to a stopped row

@@ -429,6 +429,119 @@ int weight_kband(const float* wp, int kap, int ncp, int BN, int* band, hipStream
     return AMP_OK;
 }
 
+// ---- the same three builders for G channels in one launch each (amp_bamp_trials_ch_run /
+// amp_scamp_trials_ch_run): channel g = blockIdx.y (blockIdx.z for the band scan) reads its source at
+// src + g * sg and writes its MFMA-packed operator at wt + g * dg (64-bit offsets) and its band ranges
+// at band + g * bstride.  Every value is formed as in the single-channel kernels above: a channel's
+// operator and ranges have the bits a call of build_cweight / build_abs2_weight / weight_kband on that
+// channel alone gives. ----
+
+__global__ void build_cweight_ch_kernel(const float2* __restrict__ src, size_t sg, long so, long sj, int conj, int O,
+                                        int J, float* __restrict__ wt, size_t dg, int kap, int ncp) {
+    src += (size_t)blockIdx.y * sg;
+    wt += (size_t)blockIdx.y * dg;
+    const long total = (long)(ncp / 2) * (kap / 2);
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int o = (int)(e / (kap / 2)), j = (int)(e % (kap / 2));
+        float xr = 0.f, xi = 0.f;
+        if (o < O && j < J) {
+            const float2 v = src[o * so + j * sj];
+            xr = v.x;
+            xi = conj ? -v.y : v.y;
+        }
+        wt[wpack_index(2 * o, 2 * j, kap)] = xr;
+        wt[wpack_index(2 * o, 2 * j + 1, kap)] = -xi;
+        wt[wpack_index(2 * o + 1, 2 * j, kap)] = xi;
+        wt[wpack_index(2 * o + 1, 2 * j + 1, kap)] = xr;
+    }
+}
+
+__global__ void build_abs2_ch_kernel(const float2* __restrict__ src, size_t sg, long so, long sj, int O, int J,
+                                     float* __restrict__ wt, size_t dg, int kap, int ncp) {
+    src += (size_t)blockIdx.y * sg;
+    wt += (size_t)blockIdx.y * dg;
+    const long total = (long)ncp * kap;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int o = (int)(e / kap), j = (int)(e % kap);
+        float v = 0.f;
+        if (o < O && j < J) {
+            const float2 z = src[o * so + j * sj];
+            const float a = (float)sqrt((double)z.x * z.x + (double)z.y * z.y);
+            v = a * a;
+        }
+        wt[wpack_index(o, j, kap)] = v;
+    }
+}
+
+// weight_kband_kernel with the channel on blockIdx.z
+__global__ __launch_bounds__(256) void weight_kband_ch_kernel(const float4* __restrict__ wp, size_t dg4, int G, int cgs,
+                                                              int gps, int* __restrict__ band, int bstride) {
+    __shared__ int s_lo, s_hi;
+    wp += (size_t)blockIdx.z * dg4;
+    band += (size_t)blockIdx.z * bstride;
+    if (threadIdx.x == 0) { s_lo = G; s_hi = -1; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cg0 = blockIdx.x * cgs;
+    const int ga = blockIdx.y * gps, gn = min(gps, G - ga);
+    int lo = G, hi = -1;
+    for (int b = wave; b < cgs * gn; b += blockDim.x >> 6) {   // wave-uniform
+        const int cg = cg0 + b / gn, g = ga + b % gn;
+        const float4 v = wp[((size_t)cg * G + g) * 64 + lane];
+        const bool nz = (v.x != 0.f) | (v.y != 0.f) | (v.z != 0.f) | (v.w != 0.f) | (v.x != v.x) | (v.y != v.y) |
+                        (v.z != v.z) | (v.w != v.w);
+        if (__any(nz)) { lo = min(lo, g); hi = max(hi, g); }
+    }
+    if (lane == 0) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_hi >= 0) {
+        atomicMin(&band[2 * blockIdx.x], s_lo);
+        atomicMax(&band[2 * blockIdx.x + 1], s_hi);
+    }
+}
+
+int build_cweight_ch(const float2* src, size_t sg, long so, long sj, int conj, int O, int J, float* wt, size_t dg,
+                     int kap, int ncp, int nch, hipStream_t st) {
+    AMP_REQUIRE(kap % GBK == 0 && ncp % 128 == 0 && nch >= 1 && nch <= WCH_MAX,
+                "build_cweight_ch: kap %d / ncp %d not tiled, or %d channels", kap, ncp, nch);
+    const long total = (long)(ncp / 2) * (kap / 2);
+    const int grid = (int)std::min<long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(build_cweight_ch_kernel, dim3(grid, nch), dim3(256), 0, st, src, sg, so, sj, conj, O, J, wt, dg,
+                       kap, ncp);
+    AMP_LAUNCH_CHECK("build_cweight_ch");
+    return AMP_OK;
+}
+
+int build_abs2_weight_ch(const float2* src, size_t sg, long so, long sj, int O, int J, float* wt, size_t dg, int kap,
+                         int ncp, int nch, hipStream_t st) {
+    AMP_REQUIRE(kap % GBK == 0 && ncp % 128 == 0 && nch >= 1 && nch <= WCH_MAX,
+                "build_abs2_weight_ch: kap %d / ncp %d not tiled, or %d channels", kap, ncp, nch);
+    const long total = (long)ncp * kap;
+    const int grid = (int)std::min<long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(build_abs2_ch_kernel, dim3(grid, nch), dim3(256), 0, st, src, sg, so, sj, O, J, wt, dg, kap, ncp);
+    AMP_LAUNCH_CHECK("build_abs2_weight_ch");
+    return AMP_OK;
+}
+
+// band: [nch][bstride] ints, bstride even and >= 2 ncp / BN.  The init and conversion launches run
+// over the whole array (the pad entries of a channel's slot become the empty range [0, 0)).
+int weight_kband_ch(const float* wp, size_t dg, int kap, int ncp, int BN, int* band, int bstride, int nch,
+                    hipStream_t st) {
+    AMP_REQUIRE(kap % GBK == 0 && ncp % BN == 0 && BN % 32 == 0 && dg % 4 == 0 && bstride % 2 == 0 &&
+                    bstride >= 2 * (ncp / BN) && nch >= 1 && nch <= WCH_MAX,
+                "weight_kband_ch: kap %d / ncp %d / BN %d / stride %d / %d channels", kap, ncp, BN, bstride, nch);
+    const int nt = ncp / BN, G = kap / 8;
+    const long slots = (long)nch * (bstride / 2);
+    AMP_REQUIRE(slots <= 0x7fffffffL, "weight_kband_ch: %ld band slots", slots);
+    const int gps = 64;
+    hipLaunchKernelGGL(weight_kband_init, dim3(cdiv((int)slots, 256)), dim3(256), 0, st, band, (int)slots, G);
+    hipLaunchKernelGGL(weight_kband_ch_kernel, dim3(nt, cdiv(G, gps), nch), dim3(256), 0, st, (const float4*)wp, dg / 4,
+                       G, BN / 32, gps, band, bstride);
+    hipLaunchKernelGGL(weight_kband_fin, dim3(cdiv((int)slots, 256)), dim3(256), 0, st, band, (int)slots);
+    AMP_LAUNCH_CHECK("weight_kband_ch");
+    return AMP_OK;
+}
+
 // [lo, hi] 32-groups -> [kb, ke) in reduction elements, whole 64-element pairs
 __global__ __launch_bounds__(256) void h2_kband_fin(int* __restrict__ band, int ntiles) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;

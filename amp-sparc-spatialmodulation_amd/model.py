@@ -88,7 +88,8 @@ def svd_gram(A: torch.Tensor, max_cond: float = 20.0):
 class Model(nn.Module):
     def __init__(self, config: Config, detector: str = 'vamp', path: str | None = None, amp=None,
                  seed: int | None = None, rng: str = 'host', group_epochs: bool = False,
-                 shard: str = 'epochs', group_trials: int = 0) -> None:
+                 shard: str = 'epochs', group_trials: int = 0, trial_channels: int = 0,
+                 trials_ws_limit: int = 4 << 30) -> None:
         """rng='host' (default): the reference's numpy / torch-CPU random streams, bit for bit
         (parity mode).  rng='device': channel, messages and noise drawn on the GPU and the SVD
         on the GPU through the Gram matrix's eigendecomposition (svd_gram; throughput mode: same
@@ -101,6 +102,15 @@ class Model(nn.Module):
         channel detected as independent trials in one launch sequence (forward_trials), in chunks
         of at most group_trials; every trial keeps its own scalars, shift and exit, so the sweep
         equals the per-epoch loop.  res = 1 degenerates to single forward calls.
+        trial_channels (> 0, with group_trials = n, BAMP / SCAMP; opt-in): one forward_trials call may
+        hold the trials of up to trial_channels whole `res` blocks, each with its own channel, and at
+        most n trials (forward_trials(..., per_channel=res): amp_bamp_trials_ch_run /
+        amp_scamp_trials_ch_run), so the reference's default res = 1 is a channel per trial.  The
+        inputs are still drawn in the reference's order and the Losses yielded in epoch order; a
+        block longer than n goes through the single-channel chunks above.  The packed operators of G
+        channels cost G times one channel's bytes: the channels per call are capped so that the
+        library's workspace query stays under trials_ws_limit bytes (a setting; default 4 GiB).
+        'vamp' raises: its trial engine would need per-channel singular values in its scalar chain.
         shard (with torch.distributed): 'epochs' (default) gives each rank whole epochs with its
         own random stream and merges the metrics once per SNR point; 'trials' (SURVEY §8(e)
         exact-compat, VAMP / BAMP / SCAMP) gives every rank the SAME epochs (one seed) and splits each batch's
@@ -156,12 +166,25 @@ class Model(nn.Module):
             N, n = config.Nt * config.Lin, config.Nr * config.Lout
             self.group_cap = self.amp.max_epochs(min(n, N))
         self.trials_cap = 0
+        self.channels_cap = 0
+        self.trials_ws_limit = int(trials_ws_limit)
+        self._blocks_cap = {}
+        if trial_channels:
+            if trial_channels < 0:
+                raise ValueError(f'trial_channels must be >= 0, got {trial_channels}')
+            if not group_trials:
+                raise ValueError('trial_channels: set group_trials (the most trials per call) as well')
+            if detector not in ('bamp', 'scamp'):
+                raise ValueError('trial_channels: trial batches over several channels are built for the BAMP and '
+                                 'SCAMP detectors (VAMP would need per-channel singular values in its scalar chain)')
+            self.channels_cap = int(trial_channels)
         if group_trials:
             if group_trials < 0:
                 raise ValueError(f'group_trials must be >= 0, got {group_trials}')
-            if config.B != 1 or detector not in ('vamp', 'bamp') or not hasattr(self.amp, 'forward_trials'):
+            dets = ('vamp', 'bamp', 'scamp') if self.channels_cap else ('vamp', 'bamp')
+            if config.B != 1 or detector not in dets or not hasattr(self.amp, 'forward_trials'):
                 raise ValueError('group_trials: independent-trial batches are built for the VAMP and BAMP '
-                                 'detectors at config.B == 1')
+                                 'detectors at config.B == 1 (SCAMP with trial_channels > 0)')
             if shard == 'trials' or group_epochs:
                 raise ValueError('group_trials does not combine with group_epochs or trial sharding')
             self.trials_cap = int(group_trials)
@@ -246,6 +269,69 @@ class Model(nn.Module):
             run.append(self._inputs(SNR, new))
         yield from flush()
 
+    def _blocks_per_call(self, res: int) -> int:
+        """The most whole `res` blocks one forward_trials call holds: at most channels_cap blocks and
+        trials_cap trials, and the workspace query of that call within trials_ws_limit (a detector
+        without the query, such as a test's stand-in, is not capped by it)."""
+        k = self._blocks_cap.get(res)
+        if k is None:
+            k = max(1, min(self.channels_cap, self.trials_cap // res))
+            query = getattr(self.amp, 'trials_workspace_bytes', None)
+            while k > 1 and query is not None and query(k * res, res) > self.trials_ws_limit:
+                k -= 1
+            self._blocks_cap[res] = k
+        return k
+
+    def _detect_trials(self, SNR: float, chans: list, run: list, per_channel):
+        """One detection of the trials `run` ([(x, sym, idx, y)]): the plain forward for one trial,
+        the single-channel forward_trials for one channel, else the several-channel form."""
+        head = (self._W,) if self.detector == 'scamp' else ()
+        if len(run) == 1:
+            x, sym, idx, y = run[0]
+            ch = self._svd if self.detector == 'vamp' else head + (chans[0],)
+            yield self.amp(*ch, y, SNR, x, sym, idx)
+            return
+        cols = [[v[j] for v in run] for j in (3, 0, 1, 2)]        # ys, xs, symbols, indices
+        if len(chans) == 1:
+            ch = self._svd if self.detector == 'vamp' else head + (chans[0],)
+            yield from self.amp.forward_trials(*ch, cols[0], SNR, *cols[1:])
+        else:
+            yield from self.amp.forward_trials(*head, list(chans), cols[0], SNR, *cols[1:], per_channel=per_channel)
+
+    def _group_trial_channels(self, SNR: float, ids: list, res: int):
+        """_group_trials with several channels per call (trial_channels > 0): the epochs `ids`, each
+        drawn in the reference's call order; up to _blocks_per_call(res) whole `res` blocks, each with
+        its own channel, go through one forward_trials call (a short last block closes its call: trial
+        e uses channel e // res).  A block longer than trials_cap goes through single-channel chunks.
+        Yields the epochs' Losses in order."""
+        chans, run = [], []
+
+        def flush():
+            if run:
+                yield from self._detect_trials(SNR, chans, run, res)
+            chans.clear()
+            run.clear()
+
+        if res > self.trials_cap:
+            for i in ids:
+                new = i % res == 0
+                if new or len(run) >= self.trials_cap:
+                    yield from flush()
+                run.append(self._inputs(SNR, new))
+                if not chans:
+                    chans.append(self._A)
+            yield from flush()
+            return
+        cap = self._blocks_per_call(res)
+        for i in ids:
+            new = i % res == 0
+            if new and len(chans) >= cap:
+                yield from flush()
+            run.append(self._inputs(SNR, new))
+            if new or not chans:
+                chans.append(self._A)
+        yield from flush()
+
     def _per_epoch_channels(self) -> bool:
         """Whether one launch may hold epochs with different channels (VAMP.epochs_channels_eligible)."""
         if self._ch_ok is None:
@@ -313,6 +399,9 @@ class Model(nn.Module):
             mine = [i for i in range(epochs) if (i // res) % self._epoch_world == self.rank % self._epoch_world]
             if self.group_cap > 1:
                 for loss in self._group(SNR, mine, res):      # side by side, chunks of group_cap epochs
+                    self.loss.accumulate(loss)
+            elif self.trials_cap > 0 and self.channels_cap > 0:
+                for loss in self._group_trial_channels(SNR, mine, res):   # several channels per call
                     self.loss.accumulate(loss)
             elif self.trials_cap > 0:
                 for loss in self._group_trials(SNR, mine, res):   # independent trials per channel run

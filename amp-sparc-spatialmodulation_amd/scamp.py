@@ -17,7 +17,7 @@ from torch import nn
 import amp_native as nat
 from config import Config
 from loss import Loss
-from vamp import _FUSED_DECIDE, LazyResult, ShardHook, _c64, block_denoise
+from vamp import _FUSED_DECIDE, LazyResult, ShardHook, _c64, _channel_stack, block_denoise
 
 
 class _Buffers:
@@ -188,7 +188,15 @@ class SCAMP(LazyResult, nn.Module):
         self.last = T
         return self.L
 
-    def forward_trials(self, W: torch.Tensor, A: torch.Tensor, ys, SNR: float, xs, symbols, indices) -> list:
+    def trials_workspace_bytes(self, trials: int, per_channel: int) -> int:
+        """Workspace bytes of a forward_trials call of `trials` trials at `per_channel` per channel
+        (amp_scamp_trials_ch_workspace_bytes; 0: the call would be refused)."""
+        d = self.config.dims()
+        return int(nat.lib().amp_scamp_trials_ch_workspace_bytes(C.byref(d), self.config.N_Layers, int(trials),
+                                                                 int(per_channel)))
+
+    def forward_trials(self, W: torch.Tensor, A, ys, SNR: float, xs, symbols, indices,
+                       per_channel: int | None = None) -> list:
         """E independent single-trial detections that share ONE channel (W, A) and one SNR, in one
         launch sequence (amp_scamp_trials_run) — the epochs of one `res` block of the reference's
         driver, which runs batch = 1 (scamp_model.py:88, 95).  Each trial is the B = 1 forward of
@@ -196,18 +204,36 @@ class SCAMP(LazyResult, nn.Module):
         iteration count (scamp.py:105), decided on xmap (scamp.py:107) and counted as Loss at B = 1
         in generator_mode 'sparc' or 'segmented'.  Returns E Loss objects (in order) that equal E
         sequential forward() calls on the launch engine; they resolve lazily.  ys / xs / symbols /
-        indices as VAMP.forward_trials.  ValueError unless config.B == 1."""
+        indices as VAMP.forward_trials.  ValueError unless config.B == 1.
+        Several channels (amp_scamp_trials_ch_run): A a list of G matrices or one [G, n, N] tensor
+        together with per_channel = R; trial e then uses channel e // R (the last channel may hold
+        fewer than R trials; R = 1 is a channel per trial), and each trial still equals its own
+        forward() with its own channel.  W stays ONE matrix: channel.py:80-83 builds it from the
+        config alone, so every channel of a config has the same W.  ValueError unless
+        G == ceil(E / R).  A single matrix without per_channel is the one-channel call."""
         E = self._trials_check(ys, xs, symbols, indices)
+        multi = per_channel is not None or isinstance(A, (list, tuple))
+        if multi:
+            if isinstance(W, (list, tuple)):
+                raise ValueError('forward_trials: W is ONE [Lout, Lin] matrix for all channels (the reference builds '
+                                 'it from the config alone)')
+            Ac, R, n, N = _channel_stack(A, E, per_channel, 'A')
         dev = ys[0].device
         with torch.cuda.device(dev):
             cfg = self.config
-            n, N = A.shape[-2], A.shape[-1]
-            Ac = _c64(A, (n, N))
+            if multi:
+                Ac = Ac.to(dev)
+            else:
+                n, N = A.shape[-2], A.shape[-1]
+                Ac = _c64(A, (n, N))
             Wc = W.reshape(cfg.Lout, cfg.Lin).to(device=dev, dtype=torch.float32).resolve_neg().contiguous()
             y, x, sym, idx, res, host, dec = self._trials_inputs(ys, xs, symbols, indices, E, n, dev)
             d, cst = cfg.dims(), cfg.constellation()
             lib = nat.lib()
-            wsb = lib.amp_scamp_trials_workspace_bytes(C.byref(d), cfg.N_Layers, E)
+            if multi:
+                wsb = lib.amp_scamp_trials_ch_workspace_bytes(C.byref(d), cfg.N_Layers, E, R)
+            else:
+                wsb = lib.amp_scamp_trials_workspace_bytes(C.byref(d), cfg.N_Layers, E)
             if wsb == 0:
                 raise ValueError('amp_scamp_trials_workspace_bytes: invalid dimensions')
             ws = nat.WORKSPACE.get(dev, 'scamp_trials', wsb)
@@ -223,8 +249,12 @@ class SCAMP(LazyResult, nn.Module):
             a.xmap, a.xmmse, a.psi = nat.dptr(xmap), nat.dptr(xm), nat.dptr(psi)
             a.status = nat.dptr(res)
             a.ws, a.ws_bytes = nat.dptr(ws), ws.numel()
-            nat.check(lib.amp_scamp_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
-                                               nat.stream_ptr(dev)), 'amp_scamp_trials_run')
+            if multi:
+                nat.check(lib.amp_scamp_trials_ch_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E, R,
+                                                      nat.stream_ptr(dev)), 'amp_scamp_trials_ch_run')
+            else:
+                nat.check(lib.amp_scamp_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
+                                                   nat.stream_ptr(dev)), 'amp_scamp_trials_run')
             out = self._trials_losses(res, host, E, dev)
             self._trials_keep = (y, x, sym, idx, Ac, Wc)   # alive until the kernels have read them
             self.last_trials = (xmap.view(E, 1, N, 1), xm.view(E, 1, N, 1), psi.view(E, 1, cfg.Lin, 1))

@@ -36,6 +36,28 @@ def _c64(t: torch.Tensor, shape) -> torch.Tensor:
     return t.resolve_conj().resolve_neg().contiguous()
 
 
+def _channel_stack(H, E: int, per_channel, what: str):
+    """The channels of a forward_trials call over several channels (BAMP / SCAMP): `H` a list of G
+    [n, N] matrices or one [G, n, N] tensor, trial e using channel e // per_channel.  Returns
+    (c64 [G, n, N] contiguous, per_channel, n, N); ValueError unless G == ceil(E / per_channel),
+    raised before any tensor is touched."""
+    if per_channel is None or int(per_channel) < 1:
+        raise ValueError(f'forward_trials: {what} given as several channels needs per_channel >= 1 '
+                         f'(got {per_channel!r})')
+    R = int(per_channel)
+    mats = list(H) if isinstance(H, (list, tuple)) else None
+    G = len(mats) if mats is not None else (H.shape[0] if H.dim() == 3 else 1)
+    want = -(-E // R)
+    if G != want:
+        raise ValueError(f'forward_trials: {G} channels for {E} trials at per_channel = {R} '
+                         f'(trial e uses channel e // per_channel: expected {want})')
+    one = mats[0] if mats is not None else H
+    n, N = one.shape[-2], one.shape[-1]
+    if mats is None:
+        return _c64(H, (G, n, N)), R, n, N              # no copy of a contiguous c64 [G, n, N]
+    return torch.stack([_c64(m, (n, N)) for m in mats]).contiguous(), R, n, N
+
+
 _FUSED_DECIDE = os.environ.get('AMP_FUSED_DECIDE', '1') != '0'
 
 

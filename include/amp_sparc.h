@@ -557,6 +557,24 @@ int amp_bamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp
 size_t amp_scamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials);
 int amp_scamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
                          const amp_trials_decide_args* dec, int32_t trials, void* stream);
+/* ---- Independent-trial batches over SEVERAL channels (BAMP, SCAMP) — the reference's drivers
+ *      redraw the channel every `res` epochs (bamp_model.py:44-67, scamp_model.py:43-66; res
+ *      defaults to 1).  Trial e uses channel e / per_channel: G = ceil(trials / per_channel)
+ *      channels, the last one possibly with fewer trials; per_channel = 1 is a channel per trial.
+ *      a->H (BAMP) / a->A (SCAMP): c64 [G][n][N], the channels back to back; SCAMP's a->W is ONE
+ *      [Lout][Lin] matrix for all channels (channel.py:80-83 builds it from the config alone).
+ *      Everything else as amp_bamp_trials_run / amp_scamp_trials_run: every trial is bit for bit
+ *      its own B = 1 forward on the launch engine with its own channel.  The operators of all G
+ *      channels are packed in a number of launches that does not depend on G and cost G times the
+ *      single-channel bytes (the _ch_workspace_bytes query; with per_channel >= trials it returns
+ *      exactly the single-channel query's bytes; 0 where the run would refuse).  AMP_E_ARG as the
+ *      single-channel entry points, plus per_channel < 1 and G > 65535 (a grid axis). */
+size_t amp_bamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel);
+int amp_bamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
+                           const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream);
+size_t amp_scamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel);
+int amp_scamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
+                            const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream);
 
 /* ---- Element-wise shrinkage denoisers — replace Shrink (shrink.py:8-166).
  * r: [count] complex64 (is_complex != 0) or float32; cov: cov_vec [count] float32, or
