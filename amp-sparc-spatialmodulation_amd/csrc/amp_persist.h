@@ -90,6 +90,11 @@ __device__ __forceinline__ int pl_mask(int ldx) {
     const int b = n & -n;
     return (b < 16 ? b : 16) - 1;
 }
+constexpr int pl_mask_c(int ldx) {   // pl_mask of a compile-time row length
+    const int n = ldx >> 3;
+    const int b = n & -n;
+    return (b < 16 ? b : 16) - 1;
+}
 __device__ __forceinline__ int pl_col(int row, int j, int m) { return j ^ ((row & m) << 3); }
 // The permuted addresses are cheap to form but loop-invariant, so the compiler would hoist every
 // one of them out of the persistent engines' iteration loop and keep it live across the denoiser
@@ -196,6 +201,114 @@ __device__ __forceinline__ void x3_store_acc(unsigned short* sP, int ldx, int o,
         split3x2(odd ? gi[h] : mi, odd ? mi : gi[h], q[3], q[4], q[5]);
 #pragma unroll
         for (int f = 0; f < 6; ++f) *reinterpret_cast<unsigned*>(p + f * pl) = q[f];
+    }
+}
+
+// ---- the A operand of vamp_persist's eight-wave bf16x3 form (one workgroup per CU) ----
+// split3x2 without the per-value finite test: the pieces of a finite value are split3x2's bit for
+// bit (its selects keep r1 there); returns the unmasked first residuals for the caller's item test.
+__device__ __forceinline__ f32x2_t split3x2_raw(float x, float y, unsigned& p0, unsigned& p1, unsigned& p2) {
+    const f32x2_t v = {x, y};
+    const bf16x2_t b0 = __builtin_convertvector(v, bf16x2_t);
+    const f32x2_t r1 = v - __builtin_convertvector(b0, f32x2_t);
+    const bf16x2_t b1 = __builtin_convertvector(r1, bf16x2_t);
+    const f32x2_t r2 = r1 - __builtin_convertvector(b1, f32x2_t);
+    const bf16x2_t b2 = __builtin_convertvector(r2, bf16x2_t);
+    p0 = __builtin_bit_cast(unsigned, b0);
+    p1 = __builtin_bit_cast(unsigned, b1);
+    p2 = __builtin_bit_cast(unsigned, b2);
+    return r1;
+}
+
+// The item test: does any lane of this wave hold a value that split3x2 would mask?  s: the packed
+// sum of the item's unmasked first residuals x - bf16(x).  For a finite x the residual is finite
+// (|x - bf16(x)| <= 2^-8 |x|: a sum of them cannot overflow) or, where x rounds to bf16 inf, -+inf,
+// which split3x2 keeps as well; for x = +-inf it is inf - inf and for a NaN it is NaN: always NaN.
+// A NaN survives every addition, so the sum is NaN whenever a value of the item is non-finite.  It
+// is NaN besides only when residuals +inf and -inf meet (two finite values that overflow bf16 with
+// opposite signs): a false positive, which takes the masked form, whose bits are split3x2's.  One
+// wave-uniform branch per item, so the lanes of a wave with nothing to mask never run the selects.
+__device__ __forceinline__ bool x3_item_masked(f32x2_t s) {
+    const float t = s.x + s.y;
+    return __builtin_amdgcn_ballot_w64(t != t) != 0;
+}
+
+// x3_store8 in that form, the plane geometry a compile-time constant (LDX = N): the six stores
+// share one address register (plane f at the immediate offset 32 f LDX bytes).
+template <int LDX>
+__device__ __forceinline__ void x3_store8_item(unsigned short* sP, int row, int j0, const float (&re)[8],
+                                               const float (&im)[8]) {
+    static_assert(5 * 32 * LDX < 65536, "the plane offsets are DS immediates");
+    u32x4 q[6];
+    f32x2_t s;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        unsigned a0, a1, a2, b0, b1, b2;
+        const f32x2_t ra = split3x2_raw(re[2 * h], re[2 * h + 1], a0, a1, a2);
+        const f32x2_t rb = split3x2_raw(im[2 * h], im[2 * h + 1], b0, b1, b2);
+        s = h == 0 ? ra + rb : s + ra + rb;
+        q[0][h] = a0; q[1][h] = a1; q[2][h] = a2; q[3][h] = b0; q[4][h] = b1; q[5][h] = b2;
+    }
+    if (__builtin_expect(x3_item_masked(s), 0)) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            unsigned a0, a1, a2, b0, b1, b2;
+            split3x2(re[2 * h], re[2 * h + 1], a0, a1, a2);
+            split3x2(im[2 * h], im[2 * h + 1], b0, b1, b2);
+            q[0][h] = a0; q[1][h] = a1; q[2][h] = a2; q[3][h] = b0; q[4][h] = b1; q[5][h] = b2;
+        }
+    }
+    const int rw = pl_opaque(row);
+    unsigned short* p = sP + rw * LDX + pl_col(rw, j0, pl_mask_c(LDX));
+#pragma unroll
+    for (int f = 0; f < 6; ++f) *reinterpret_cast<u32x4*>(p + f * 16 * LDX) = q[f];
+}
+
+// dpp_swap_pair with no `old` operand (every lane of a quad has a source: the value is never read),
+// so no register is cleared in front of each swap.
+__device__ __forceinline__ float dpp_swap_pair_u(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));
+}
+
+// x3_store_acc in that form (one item = one accumulator tile: this lane's eight split values).
+template <int LDX>
+__device__ __forceinline__ void x3_store_acc_item(unsigned short* sP, int o, const float (&vr)[4], const float (&vi)[4]) {
+    static_assert(5 * 32 * LDX + 2 * LDX < 65536, "the plane and row offsets are DS immediates");
+    const int lane = pl_opaque((int)threadIdx.x) & 63;
+    const bool odd = (lane & 1) != 0;
+    float xr[2][2], xi[2][2];   // [h]: the column pair's (even, odd) values of row row0 + h
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float gr = dpp_swap_pair_u(odd ? vr[h] : vr[2 + h]);
+        const float gi = dpp_swap_pair_u(odd ? vi[h] : vi[2 + h]);
+        const float mr = odd ? vr[2 + h] : vr[h], mi = odd ? vi[2 + h] : vi[h];
+        xr[h][0] = odd ? gr : mr; xr[h][1] = odd ? mr : gr;
+        xi[h][0] = odd ? gi : mi; xi[h][1] = odd ? mi : gi;
+    }
+    unsigned q[2][6];
+    f32x2_t s;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const f32x2_t ra = split3x2_raw(xr[h][0], xr[h][1], q[h][0], q[h][1], q[h][2]);
+        const f32x2_t rb = split3x2_raw(xi[h][0], xi[h][1], q[h][3], q[h][4], q[h][5]);
+        s = h == 0 ? ra + rb : s + ra + rb;
+    }
+    if (__builtin_expect(x3_item_masked(s), 0)) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            split3x2(xr[h][0], xr[h][1], q[h][0], q[h][1], q[h][2]);
+            split3x2(xi[h][0], xi[h][1], q[h][3], q[h][4], q[h][5]);
+        }
+    }
+    // rows row0, row0 + 1 (row0 even): the same permuted column unless the mask's low bit tells
+    // them apart, so row0 + 1 keeps a column of its own
+    const int row0 = 4 * (lane >> 4) + (odd ? 2 : 0);
+    constexpr int m = pl_mask_c(LDX);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        unsigned short* p = sP + (row0 + h) * LDX + pl_col(row0 + h, o & ~1, m);
+#pragma unroll
+        for (int f = 0; f < 6; ++f) *reinterpret_cast<unsigned*>(p + f * 16 * LDX) = q[h][f];
     }
 }
 

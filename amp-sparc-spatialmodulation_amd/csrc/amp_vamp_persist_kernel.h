@@ -42,6 +42,9 @@ constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iter
 #ifndef AMP_X3_DU
 #define AMP_X3_DU 2                     // 16-QAM sections in flight per lane group (bf16x3 engine; 4 measured: no gain)
 #endif
+#ifndef AMP_X3_W8_AOP
+#define AMP_X3_W8_AOP 1                 // the eight-wave form's A-operand phases on constants (A/B builds: 0)
+#endif
 #ifndef AMP_SCALAR_TAIL
 #define AMP_SCALAR_TAIL 1               // bf16x3 at one workgroup per CU: the LMMSE scalars of vamp_advance inside the
 #endif                                  // next iteration's GEMM1, behind group 0 (A/B builds: 0, the unsplit form)
@@ -76,6 +79,18 @@ __host__ __device__ inline PLayout playout(int N, int k, int L, bool x3 = false)
     y.offScr = o; o += 1024;
     y.total = o;
     return y;
+}
+
+// The part of the carve that N alone fixes in the bf16x3 engine (k == N): playout(N, N, L, true)'s
+// ldr, offR, offX and the plane row length, as constants.
+struct AopLayout {
+    int ldx, ldr, offR, offX;
+};
+constexpr AopLayout aop_layout(int N) {
+    const int lda = 2 * N + 4, ldr = 2 * N + 8;
+    const int planes = 6 * 16 * N / 2;
+    const int offR = planes > PBM * lda ? planes : PBM * lda;
+    return AopLayout{N, ldr, offR, offR + PBM * ldr};
 }
 
 // dc: the decision table; its Const64 base is also the exact rare path's float64 constellation.
@@ -135,6 +150,13 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // r_epi, inv_sigma2 for the denoiser) follow inside the next iteration's GEMM1 (DESIGN.md §3.1:
     // -3.6 to -10 us per cfg4 step, though the traced GEMM1 grows by the tail's length)
     constexpr int STAIL = (X3PF && OCC == 1) ? AMP_SCALAR_TAIL : 0;
+    // the eight-wave bf16x3 form at one workgroup per CU: the A operand's phases (r~ build, w store,
+    // the GEMMs' fragment reads, r_epi) take the item split (amp_persist.h x3_store8_item) and the
+    // geometry that N = k = 8 NT NWV fixes as constants, so that plane and row offsets are DS
+    // immediates (persist_launch_t checks P against them); the other phases keep the run-time carve
+    constexpr bool AOP = X3PF && NWV == 8 && OCC == 1 && AMP_X3_W8_AOP;
+    constexpr int CN = 8 * NT * NWV;
+    constexpr AopLayout CY = aop_layout(CN);
 #define c64 (static_cast<const Const64&>(*Dp))
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_flag;
@@ -530,6 +552,22 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 __builtin_amdgcn_sched_barrier(0);
             }
             const int tdx = NWV == 8 ? pl_opaque(tid) : tid;   // eight waves: addresses formed here
+            if constexpr (AOP) {
+                static_assert(PBM * (CN >> 3) == PWG, "one item per thread");
+                const int row = tdx % PBM, j0 = 8 * (tdx / PBM);
+                const float* rp = lds + CY.offR + row * CY.ldr + 2 * j0;   // (x~'s rows CY.offX - CY.offR above r's)
+                float re[8], im[8];
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const float4 x = *reinterpret_cast<const float4*>(rp + (CY.offX - CY.offR) + 4 * h);
+                    const float4 q = *reinterpret_cast<const float4*>(rp + 4 * h);
+                    re[2 * h] = (x.x - cur.dxdr_prev * q.x) * cur.ns_prev;
+                    im[2 * h] = (x.y - cur.dxdr_prev * q.y) * cur.ns_prev;
+                    re[2 * h + 1] = (x.z - cur.dxdr_prev * q.z) * cur.ns_prev;
+                    im[2 * h + 1] = (x.w - cur.dxdr_prev * q.w) * cur.ns_prev;
+                }
+                x3_store8_item<CY.ldx>(sP, row, j0, re, im);
+            } else
             for (int e = tdx; e < PBM * (N >> 3); e += PWG) {   // 8 complex values per item
                 // consecutive items walk the 16 rows (row stride 2N + 4 floats): each group of 16
                 // lanes reads 16 different bank quads (item-major rows put 4 lanes on each)
@@ -583,9 +621,9 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                         stamp(t, 9);
                     }
                 };
-                gemm_x3_ring<NC, G3, X3R, X3PIN, true, true>(sP, ldx, Wx1, cc0, wring, cr, ci, Wx2, X3NoHook(), tail0);
+                gemm_x3_ring<NC, G3, X3R, X3PIN, true, true>(sP, AOP ? CY.ldx : ldx, Wx1, cc0, wring, cr, ci, Wx2, X3NoHook(), tail0);
             } else
-            gemm_x3_ring<NC, G3, X3R, X3PIN, true, true>(sP, ldx, Wx1, cc0, wring, cr, ci, Wx2);
+            gemm_x3_ring<NC, G3, X3R, X3PIN, true, true>(sP, AOP ? CY.ldx : ldx, Wx1, cc0, wring, cr, ci, Wx2);
             // a building forward leaves q0 for the reuse forwards that follow it: row 0 (always a
             // valid trial) of workgroup 0, lanes 0-15 of every wave
             if (__builtin_expect(t == 0 && P.q0_store != 0 && wg == 0, 0)) {
@@ -699,7 +737,8 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                     wr[r] = sc * (yt[2 * t2][r] + cur.vr * qr) - qr;
                     wi[r] = sc * (yt[2 * t2 + 1][r] + cur.vr * qi) - qi;
                 }
-                x3_store_acc(sP, ldx, o, wr, wi);
+                if constexpr (AOP) x3_store_acc_item<CY.ldx>(sP, o, wr, wi);
+                else x3_store_acc(sP, ldx, o, wr, wi);
                 if (P.dump) {
                     float* dp = P.dump + (((size_t)t * nwg + wg) * 5 + 0) * PBM * twoN;
 #pragma unroll
@@ -761,8 +800,33 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { cr[t2][r] *= hsc[r]; ci[t2][r] *= hsc[r]; }
             }
-            if constexpr (X3PF) gemm_x3_ring<NC, G3, X3R, X3PIN, true>(sP, ldx, Wx2, cc0, wring, cr, ci);
-            r_epi(cc0, cr, ci);
+            if constexpr (X3PF) gemm_x3_ring<NC, G3, X3R, X3PIN, true>(sP, AOP ? CY.ldx : ldx, Wx2, cc0, wring, cr, ci);
+            if constexpr (AOP) {
+                // r_epi with the AOP constants: row stride and the x~ / r bases (one address register
+                // per lane, the rows and tiles at immediate offsets)
+                const int lnr = pl_opaque(lane);
+                float* const rp = lds + CY.offR + 4 * (lnr >> 4) * CY.ldr + 2 * (16 * cc0 + (lnr & 15));
+#pragma unroll
+                for (int t2 = 0; t2 < NC; ++t2) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float* const pr = rp + r * CY.ldr + 32 * t2;
+                        const float* const px = pr + (CY.offX - CY.offR);
+                        const float rtr = (px[0] - cur.dxdr_prev * pr[0]) * cur.ns_prev;
+                        const float rti = (px[1] - cur.dxdr_prev * pr[1]) * cur.ns_prev;
+                        const float xtr = cr[t2][r] + rtr, xti = ci[t2][r] + rti;
+                        pr[0] = (xtr - cur.alpha * rtr) * cur.inv1ma;
+                        pr[1] = (xti - cur.alpha * rti) * cur.inv1ma;
+                        if (P.dump) {
+                            const int o = 16 * (cc0 + t2) + (lnr & 15);
+                            float* dp = P.dump + (((size_t)t * nwg + wg) * 5 + 1) * PBM * twoN;
+                            dp[(4 * (lane >> 4) + r) * twoN + 2 * o] = pr[0];
+                            dp[(4 * (lane >> 4) + r) * twoN + 2 * o + 1] = pr[1];
+                        }
+                    }
+                }
+            } else
+                r_epi(cc0, cr, ci);
         } else {
         gemm16<NT, NT * NWV>(sA, lda, P.Wq2, ct0, acc);
 #pragma unroll
@@ -868,6 +932,17 @@ template <int NT, int KK, int NWV, int DU, bool X3, int OCC = 1, bool H2 = false
 static int persist_launch_t(const VampK& P, const DecConst& dc, hipStream_t st) {
     const void* fn = (const void*)vamp_persist<NT, KK, NWV, DU, X3, OCC, H2, I8>;
     const size_t lds = (size_t)playout(P.N, P.k, P.L, X3).total * 4;
+    if constexpr (X3 && !H2 && !I8 && NWV == 8 && OCC == 1) {
+        // the kernel's A-operand phases carry this geometry as constants (AopLayout)
+        constexpr AopLayout c = aop_layout(8 * NT * NWV);
+        const PLayout y = playout(P.N, P.k, P.L, true);
+        if (P.N != 8 * NT * NWV || P.k != P.N || x3_ldx(P.N) != c.ldx || y.ldr != c.ldr || y.offA != 0 || y.offR != c.offR ||
+            y.offX != c.offX) {
+            set_error("vamp_persist: N = %d, k = %d is not the geometry of the eight-wave bf16x3 kernel (N = k = %d)", P.N, P.k,
+                      8 * NT * NWV);
+            return AMP_E_ARG;
+        }
+    }
     // the dynamic-LDS attribute and the occupancy query cost tens of us per call: once per
     // instantiation and LDS size (single-threaded host use, like the rest of the ABI)
     static size_t attr_lds = 0;

@@ -302,3 +302,65 @@ int ytil_x3_launch(const float* y, int n, int rows, const void* wq, float* ytil,
 }
 
 }  // namespace amp
+
+// Diagnostic (amp_x3_planes_debug): the A-operand plane writers of vamp_persist on caller-supplied
+// rows.  One workgroup of eight waves, N = 256, as the cfg4 kernel runs them: the row-item map of
+// the r~ build (item tid: row tid % 16, columns 8 (tid / 16) ...) and the accumulator map of the w
+// store (wave w: complex column tiles 2 w, 2 w + 1).  Form 0: x3_store8, 1: x3_store8_item,
+// 2: x3_store_acc, 3: x3_store_acc_item; each form's planes are copied out in LDS order.
+namespace amp {
+
+constexpr int XPD_N = 256, XPD_WG = 512, XPD_WORDS = 6 * PBM * XPD_N / 2;
+
+__global__ __launch_bounds__(XPD_WG) void x3_planes_debug_kernel(const float* __restrict__ rows, int nrows, int ldx,
+                                                                  unsigned* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    unsigned short* sP = reinterpret_cast<unsigned short*>(lds);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    auto at = [&](int row, int col) {   // rows past nrows are zero rows, as the engine's padded trials
+        const float2 v = *reinterpret_cast<const float2*>(rows + ((size_t)min(row, nrows - 1) * XPD_N + col) * 2);
+        return row < nrows ? v : make_float2(0.f, 0.f);
+    };
+    for (int form = 0; form < 4; ++form) {
+        if (form < 2) {
+            static_assert(PBM * (XPD_N >> 3) == XPD_WG, "one item per thread");
+            const int row = tid % PBM, j0 = 8 * (tid / PBM);
+            float re[8], im[8];
+#pragma unroll
+            for (int h = 0; h < 8; ++h) {
+                const float2 v = at(row, j0 + h);
+                re[h] = v.x; im[h] = v.y;
+            }
+            if (form == 0) x3_store8(sP, ldx, row, j0, re, im);
+            else x3_store8_item<XPD_N>(sP, row, j0, re, im);
+        } else {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int o = 16 * (2 * wave + t) + (lane & 15);
+                float vr[4], vi[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float2 v = at(4 * (lane >> 4) + r, o);
+                    vr[r] = v.x; vi[r] = v.y;
+                }
+                if (form == 2) x3_store_acc(sP, ldx, o, vr, vi);
+                else x3_store_acc_item<XPD_N>(sP, o, vr, vi);
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < XPD_WORDS; e += XPD_WG) out[(size_t)form * XPD_WORDS + e] = reinterpret_cast<const unsigned*>(sP)[e];
+        __syncthreads();
+    }
+}
+
+}  // namespace amp
+
+int amp_x3_planes_debug(const void* rows, int32_t nrows, void* planes, void* stream) {
+    using namespace amp;
+    AMP_REQUIRE(rows && planes, "amp_x3_planes_debug: null pointer argument");
+    AMP_REQUIRE(nrows >= 1 && nrows <= PBM, "amp_x3_planes_debug: nrows = %d (1 ... %d)", nrows, PBM);
+    hipLaunchKernelGGL(x3_planes_debug_kernel, dim3(1), dim3(XPD_WG), (size_t)XPD_WORDS * 4, (hipStream_t)stream,
+                       (const float*)rows, (int)nrows, x3_ldx(XPD_N), (unsigned*)planes);
+    AMP_LAUNCH_CHECK("amp_x3_planes_debug");
+    return AMP_OK;
+}

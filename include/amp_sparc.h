@@ -494,6 +494,13 @@ size_t amp_map_decide_workspace_bytes(const amp_dims* d);
 int amp_decide_debug_sections(const amp_dims* d, const amp_constellation* c, const void* xmap,
                               const void* xmmse, const void* x, int32_t narrow, void* decisions,
                               void* mismatch, void* sqerr, void* stream);
+/* Diagnostic: the six bf16 planes (the A operand of the bf16x3 GEMMs) that the persistent VAMP
+ * engine's plane writers form from caller-supplied rows, in one workgroup of eight waves at
+ * N = 256.  rows: float32 [nrows][256][2] (complex), 1 <= nrows <= 16; rows nrows ... 15 are zero
+ * rows.  planes: uint16 [4][6][16][256] in the engine's LDS order (plane f, row r, element j at
+ * column j ^ 8 (r & 15)): form 0 the shared row-item writer (x3_store8), 1 the eight-wave engine's
+ * item form of it, 2 the shared accumulator-layout writer (x3_store_acc), 3 its item form. */
+int amp_x3_planes_debug(const void* rows, int32_t nrows, void* planes, void* stream);
 /* Same counters with Loss.random_decision (loss.py:252-280, generator_mode='random'): per
  * channel use the Na largest |x_m| (NaN largest; exact ties by larger index), each decided to
  * its nearest point, compared in ascending position order with the row's true sorted indices.

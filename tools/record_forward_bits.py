@@ -3,7 +3,8 @@
 tests/test_gpu_vamp_ring_prefill.py (tests/golden/ring_prefill_bits.part<k>.npz).
 
   python tools/record_forward_bits.py [--out DIR] [--stem STEM] [--cases "Nt,Na,Nr,B,alphabet;..."] [--share-channel]
-                                      [--ebn0 "dB;..."] [--nan-row "row;..."] [--dump]
+                                      [--ebn0 "dB;..."] [--nan-row "row;..."] [--inf-entry "row,col;..."] [--dump]
+                                      [--dump-wr]
 
 --stem / --cases record another fixture (tests/golden/<stem>.part<k>.npz) for another case list;
 --share-channel draws one channel, the first case's, stores it once ('shared/U', 's', 'Vh', 'SNR')
@@ -11,6 +12,11 @@ and runs every case that agrees with it in Nt and Nr on it (another case draws a
 --ebn0 sets Eb/N0 per case (one value: every case; an empty entry: the alphabet's default) and
 stores that case's SNR as '<case>/SNR', e.g. to record a forward that stops before the cap;
 --nan-row sets one row of y to NaN per case (an empty entry: none), in both forwards;
+--inf-entry sets one entry of y to +inf per case ("row,col"; an empty entry: none), in both forwards;
+--dump-wr runs both forwards with the state dump on and stores each forward's GEMM1 epilogue w and
+GEMM2 epilogue r per iteration: the first WR_FULL iterations whole ('f<i>_it_w', 'f<i>_it_r'
+[WR_FULL, B, 2N]), every iteration as one CRC-32 per trial row ('f<i>_it_wcrc', 'f<i>_it_rcrc' [T, B])
+and whether the row of w is finite ('f<i>_it_wfin');
 --dump runs the reuse forward with the persistent engine's per-iteration state dump on and stores,
 for the iterations it ran, every valid trial's var ('f1_it_var'), each wave's float64 var sum
 ('f1_it_wsum') and the exchange records the workgroups published ('f1_it_gran').
@@ -52,11 +58,11 @@ def config(Nt, Na, Nr, B, alphabet, device):
                   channel_profile='uniform', channel_truncation='tail', device=device)
 
 
-def make_inputs(case, shared=None, ebn0=None, nan_row=None):
+def make_inputs(case, shared=None, ebn0=None, nan_row=None, inf_entry=None):
     """One channel and two epochs of messages + noise (host tensors), in the reference's call order.
     shared: the make_inputs result of another case whose channel (A, U, s, Vh, SNR) this one uses;
     ebn0: this case's own Eb/N0 (else the alphabet's default, or the shared channel's SNR);
-    nan_row: the row of y set to NaN in both epochs."""
+    nan_row: the row of y set to NaN in both epochs; inf_entry: the (row, column) of y set to +inf in both."""
     from channel import Channel
     from data import Data
     np.random.seed(SEED)
@@ -77,6 +83,8 @@ def make_inputs(case, shared=None, ebn0=None, nan_row=None):
         y = A @ x + ch.awgn(SNR)
         if nan_row is not None:
             y[nan_row] = float('nan')
+        if inf_entry is not None:
+            y[inf_entry[0], inf_entry[1]] = float('inf')
         eps.append(dict(x=x, sym=sym, idx=idx, y=y))
     return dict(A=A, U=U, s=s, Vh=Vh, SNR=SNR, eps=eps)
 
@@ -101,7 +109,17 @@ PBM = 16     # trials per persistent workgroup (csrc/amp_vamp.h)
 ITERS = 20   # config()'s iteration cap
 
 
-def dumped_forward(det, cfg, chan, SNR, ep, device):
+WR_FULL = 2  # iterations whose w and r --dump-wr stores whole
+
+
+def row_crc(a):
+    """CRC-32 of each row's bytes: a [T, B, n] -> uint32 [T, B]."""
+    import zlib
+    a = np.ascontiguousarray(a)
+    return np.array([[zlib.crc32(r.tobytes()) for r in it] for it in a], dtype=np.uint32).reshape(a.shape[:2])
+
+
+def dumped_forward(det, cfg, chan, SNR, ep, device, wr=False):
     """forward() with the persistent engine's state dump on (amp_vamp_debug_dump); adds, for the
     iterations that ran: it_var [T, B, N] float32, it_wsum [T, nwg, waves] float64 (each wave's var
     sum), it_gran [T, nwg, 8] uint32 (the exchange records: sumvar, notclose, tag, max|xi|, min max, 0, tag)."""
@@ -127,16 +145,23 @@ def dumped_forward(det, cfg, chan, SNR, ep, device):
     out['it_var'] = np.concatenate([d[:T, w, 3, :rows[w], :N] for w in range(nwg)], axis=1).copy()
     out['it_wsum'] = np.ascontiguousarray(d[:T, :, 3, 0, N:N + 2 * waves]).view(np.float64).copy()
     out['it_gran'] = gran[:T].copy()
+    if wr:   # slot 0: w (GEMM1's epilogue), slot 1: r (GEMM2's), both [16, 2N] per workgroup
+        w, r = (np.concatenate([d[:T, g, slot, :rows[g]] for g in range(nwg)], axis=1) for slot in (0, 1))
+        out['it_w'], out['it_r'] = w[:WR_FULL].copy(), r[:WR_FULL].copy()
+        out['it_wcrc'], out['it_rcrc'] = row_crc(w), row_crc(r)
+        out['it_wfin'] = np.isfinite(w).all(axis=2)
     return made, out
 
 
-def run_case(case, inp, device, dump=False):
+def run_case(case, inp, device, dump=False, wr=False):
     """A building forward, then a reuse forward with a new y on the same channel objects
-    (dump: the reuse forward with the state dump on)."""
+    (dump: the reuse forward with the state dump on; wr: both, with w and r stored too)."""
     from vamp import VAMP
     cfg = config(*case, device='cuda')
     det = VAMP(cfg)
     chan = tuple(inp[k].to(device).contiguous() for k in ('U', 's', 'Vh'))
+    if wr:
+        return [dumped_forward(det, cfg, chan, inp['SNR'], ep, device, wr=True) for ep in inp['eps']]
     res = [forward(det, chan, inp['SNR'], inp['eps'][0], device)]
     if dump:
         res.append(dumped_forward(det, cfg, chan, inp['SNR'], inp['eps'][1], device))
@@ -190,6 +215,8 @@ def main():
                     help="one channel, the first case's, stored once and used by every case")
     ap.add_argument('--ebn0', default=None, help='"dB;..." per case (one value: every case; empty: the default)')
     ap.add_argument('--nan-row', default=None, help='"row;..." per case: that row of y is NaN (empty: none)')
+    ap.add_argument('--inf-entry', default=None, help='"row,col;..." per case: that entry of y is +inf (empty: none)')
+    ap.add_argument('--dump-wr', action='store_true', help="both forwards' per-iteration w and r (see above)")
     ap.add_argument('--dump', action='store_true', help="the reuse forward's per-iteration var, wave sums and exchange records")
     args = ap.parse_args()
     cases = CASES if args.cases is None else [
@@ -205,14 +232,19 @@ def main():
         vals = args.nan_row.split(';')
         assert len(vals) == len(cases), (vals, cases)
         nan_rows = [int(v) if v.strip() else None for v in vals]
+    inf_entries = [None] * len(cases)
+    if args.inf_entry is not None:
+        vals = args.inf_entry.split(';')
+        assert len(vals) == len(cases), (vals, cases)
+        inf_entries = [tuple(int(u) for u in v.split(',')) if v.strip() else None for v in vals]
     device = torch.device('cuda', 0)
     flat = {}
     shared = None
-    for case, eb, nr in zip(cases, ebn0, nan_rows):
+    for case, eb, nr, ie in zip(cases, ebn0, nan_rows, inf_entries):
         name = case_name(*case)
         own = shared is not None and case[0:3:2] != shared['dims']   # another Nt, Nr: its own channel
-        inp = make_inputs(case, None if own else shared, eb, nr)
-        res = run_case(case, inp, device, args.dump)
+        inp = make_inputs(case, None if own else shared, eb, nr, ie)
+        res = run_case(case, inp, device, args.dump, args.dump_wr)
         print(name, 'prepares (building, reuse) per forward:', [m for m, _ in res],
               'T:', [int(o['T'][0]) for _, o in res])
         if args.share_channel and shared is None:
