@@ -161,6 +161,31 @@ __device__ __forceinline__ int group_imax_c(int v) {
 }
 template <int G>
 __device__ __forceinline__ float group_fmax_c(float v) { return funkey(group_imax_c<G>(fkey(v))); }
+// The min counterpart (v_min_i32_dpp): a negative NaN wins, callers keep NaNs away.
+template <int O>
+__device__ __forceinline__ int imin_step(int v) {
+    if constexpr (O == 16 || O == 32) {
+        const unsigned u = (unsigned)v;
+        const auto r = (O == 16) ? __builtin_amdgcn_permlane16_swap(u, u, false, false)
+                                 : __builtin_amdgcn_permlane32_swap(u, u, false, false);
+        return min((int)r[0], (int)r[1]);
+    } else {
+        return min(v, xl_i32<O>(v));
+    }
+}
+template <int G>
+__device__ __forceinline__ int group_imin_c(int v) {
+    if constexpr (G > 1) v = imin_step<1>(v);
+    if constexpr (G > 2) v = imin_step<2>(v);
+    if constexpr (G > 4) v = imin_step<4>(v);
+    if constexpr (G > 8) v = imin_step<8>(v);
+    if constexpr (G > 16) v = imin_step<16>(v);
+    if constexpr (G > 32) v = imin_step<32>(v);
+    return v;
+}
+// Keys of +inf and -inf: a key outside [FKEY_NINF, FKEY_PINF] is a NaN's (of either sign).
+constexpr int FKEY_PINF = 0x7f800000, FKEY_NINF = (int)0x807fffff;
+__device__ __forceinline__ bool part_key_nan(int k) { return k > FKEY_PINF || k < FKEY_NINF; }
 // Sum over the group (same bits in every lane: float addition is commutative) and, per lane,
 // the sum of every OTHER lane of the group: a sum of non-negative terms when the inputs are,
 // so Z - Z_m needs no subtraction.  DPP distances fuse into v_add_f32_dpp.
@@ -230,6 +255,28 @@ __device__ __forceinline__ void part_wave_reduce(PartAcc& p) {
     p.maxabs = group_max_nan(p.maxabs, 64);
     p.minsecmax = group_min_nan(p.minsecmax, 64);
     p.notclose = group_sum(p.notclose, 64);
+}
+
+// part_wave_reduce for the exchange of the eight-wave bf16x3 persistent engine (amp_persist.h
+// part_publish_keys / part_gather_keys).  maxabs and minsecmax are float32 values widened (DenStat::fold,
+// the granules' float32 words) or NaN, so without a NaN their extremes are order-free and exact as
+// integer extremes over fkey keys: one v_max_i32_dpp / v_min_i32_dpp per level where the float64
+// nan_max / nan_min take three compares, an add and four selects behind two DPP moves.  sumvar and
+// notclose keep part_wave_reduce's tree.  One wave-uniform test first: a wave that holds a NaN in
+// either value of any lane runs part_wave_reduce itself (NaN payloads and DenStat's float64 NaN come
+// out as they did).  The result equals part_wave_reduce's bit for bit except for the sign of a zero
+// extreme when zeros of both signs are present (the key order puts -0 below +0; DESIGN.md §3.1 lists
+// the consumers: each compares or subtracts).
+__device__ __forceinline__ void part_wave_reduce_keys(PartAcc& p) {
+    const float mx = (float)p.maxabs, mn = (float)p.minsecmax;   // exact, or the NaN kept a NaN
+    if (__builtin_expect(__any((mx != mx) | (mn != mn)) != 0, 0)) {
+        part_wave_reduce(p);
+        return;
+    }
+    p.sumvar = group_sum(p.sumvar, 64);
+    p.notclose = group_sum(p.notclose, 64);
+    p.maxabs = (double)funkey(group_imax_c<64>(fkey(mx)));
+    p.minsecmax = (double)funkey(group_imin_c<64>(fkey(mn)));
 }
 
 // Reduces across the 4 waves through LDS scratch (>= 4*32 bytes) and stores the

@@ -972,4 +972,129 @@ __device__ __forceinline__ bool part_gather(__amdgpu_buffer_rsrc_t rs, unsigned 
     return ok;
 }
 
+// part_publish / part_gather for the eight-wave bf16x3 engine at one workgroup per CU
+// (amp_vamp_persist_kernel.h AMP_X3_W8_XCH): the same granules, tags, stores, polling loop and
+// barriers; the extremes are reduced as fkey keys (amp_common.h part_wave_reduce_keys) wherever no
+// NaN is among them, and by part_publish's code where one is.  Thread 0's fold over the waves narrows
+// each wave's two extremes to float32 (exact) and folds their keys as integers; both extremes of
+// both key rows are kept, since a NaN's key lies above +inf's or below -inf's, and such a fold runs
+// part_publish's loop over the Partials.  sumvar keeps its serial order s[0] + s[1] + ... and the
+// Partials stay where the state dump reads them.
+template <int NW>
+__device__ __forceinline__ void part_publish_keys(PartAcc p, __amdgpu_buffer_rsrc_t rs, unsigned off, unsigned tag,
+                                                  void* lds_scratch) {
+    part_wave_reduce_keys(p);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    Partial* s = reinterpret_cast<Partial*>(lds_scratch);
+    __syncthreads();
+    if (lane == 0) {
+        s[wave].sumvar = p.sumvar; s[wave].maxabs = p.maxabs;
+        s[wave].minsecmax = p.minsecmax; s[wave].notclose = p.notclose;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sv = s[0].sumvar;
+        uint32_t nc = s[0].notclose;
+        int xhi = fkey((float)s[0].maxabs), xlo = xhi, nhi = fkey((float)s[0].minsecmax), nlo = nhi;
+#pragma unroll
+        for (int w = 1; w < NW; ++w) {
+            sv += s[w].sumvar; nc += s[w].notclose;
+            const int kx = fkey((float)s[w].maxabs), kn = fkey((float)s[w].minsecmax);
+            xhi = max(xhi, kx); xlo = min(xlo, kx);
+            nhi = max(nhi, kn); nlo = min(nlo, kn);
+        }
+        float fx = funkey(xhi), fn = funkey(nlo);
+        if (__builtin_expect(part_key_nan(xhi) || part_key_nan(xlo) || part_key_nan(nhi) || part_key_nan(nlo), 0)) {
+            double mx = s[0].maxabs, mn = s[0].minsecmax;
+            for (int w = 1; w < NW; ++w) { mx = nan_max(mx, s[w].maxabs); mn = nan_min(mn, s[w].minsecmax); }
+            fx = (float)mx; fn = (float)mn;
+        }
+        const unsigned long long b = (unsigned long long)__double_as_longlong(sv);
+        const u32x4 g0 = {(unsigned)b, (unsigned)(b >> 32), nc, tag};
+        const u32x4 g1 = {__float_as_uint(fx), __float_as_uint(fn), 0u, tag};
+        __builtin_amdgcn_raw_buffer_store_b128(g0, rs, (int)off, 0, 16);        // aux 16 = sc1
+        __builtin_amdgcn_raw_buffer_store_b128(g1, rs, (int)off + 16, 0, 16);
+    }
+}
+
+// The lane fold takes the extremes on the granules' float32 words (sumvar in part_gather's order,
+// 0.0 + g0 + g1 + g2 + g3 over lane + 64 q); one wave-uniform test over every lane's words sends a
+// sweep that holds a NaN through part_gather's fold and part_wave_reduce.  The tree is
+// part_wave_reduce_keys' (its NaN test has been made: the keys go in directly).
+__device__ __forceinline__ bool part_gather_keys(__amdgpu_buffer_rsrc_t rs, unsigned off0, int nwg, unsigned tag,
+                                                 unsigned* abort_word, PartAcc& out, void* lds_scratch, int* s_flag) {
+    Partial* s = reinterpret_cast<Partial*>(lds_scratch);
+    if ((threadIdx.x >> 6) == 0) {
+        const int lane = threadIdx.x & 63;
+        u32x4 a[4], b[4];
+        int ok_all = 1;
+        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+        for (;;) {
+            bool ok = true;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int w = lane + 64 * q;
+                if (w < nwg) {
+                    a[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off0 + 32u * w), 0, 16);
+                    b[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off0 + 32u * w + 16), 0, 16);
+                    ok &= (a[q].w == tag) & (b[q].w == tag);
+                }
+            }
+            if (__all(ok)) break;
+            if (__hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
+                __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {   // 2 s at 100 MHz
+                __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ok_all = 0;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        PartAcc p;
+        bool isnan_ = false;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (lane + 64 * q < nwg) {
+                const float fx = __uint_as_float(b[q].x), fn = __uint_as_float(b[q].y);
+                isnan_ |= (fx != fx) | (fn != fn);
+            }
+        }
+        if (__builtin_expect(__any(isnan_) != 0, 0)) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (lane + 64 * q < nwg) {
+                    p.sumvar += __longlong_as_double((long long)(((unsigned long long)a[q].y << 32) | a[q].x));
+                    p.maxabs = nan_max(p.maxabs, (double)__uint_as_float(b[q].x));
+                    p.minsecmax = nan_min(p.minsecmax, (double)__uint_as_float(b[q].y));
+                    p.notclose += a[q].z;
+                }
+            }
+            part_wave_reduce(p);
+        } else {
+            int kx = 0, kn = FKEY_PINF;   // fkey(0.0f), fkey(INFINITY): PartAcc's initial values
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (lane + 64 * q < nwg) {
+                    p.sumvar += __longlong_as_double((long long)(((unsigned long long)a[q].y << 32) | a[q].x));
+                    kx = max(kx, fkey(__uint_as_float(b[q].x)));
+                    kn = min(kn, fkey(__uint_as_float(b[q].y)));
+                    p.notclose += a[q].z;
+                }
+            }
+            p.sumvar = group_sum(p.sumvar, 64);
+            p.notclose = group_sum(p.notclose, 64);
+            p.maxabs = (double)funkey(group_imax_c<64>(kx));
+            p.minsecmax = (double)funkey(group_imin_c<64>(kn));
+        }
+        if (lane == 0) {
+            s[0].sumvar = p.sumvar; s[0].maxabs = p.maxabs; s[0].minsecmax = p.minsecmax; s[0].notclose = p.notclose;
+            *s_flag = ok_all;
+        }
+    }
+    __syncthreads();
+    out.sumvar = s[0].sumvar; out.maxabs = s[0].maxabs; out.minsecmax = s[0].minsecmax; out.notclose = s[0].notclose;
+    const bool ok = *s_flag != 0;
+    __syncthreads();
+    return ok;
+}
+
 }  // namespace amp

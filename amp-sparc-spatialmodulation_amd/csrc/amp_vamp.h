@@ -286,6 +286,48 @@ __device__ inline VampIter vamp_advance_head(const VampK& P, const VampIter& cur
     return nx;
 }
 
+// var.mean()'s quotient sumvar / (Bmean N) where the integer product Bmean N is a power of two 2^k
+// (a scalar test on the kernel arguments): ldexp(sumvar, -k).  The quotient by 2^k and the scaled
+// value are the same real number, rounded once to nearest even: the same bits for every input,
+// subnormal results, inf and NaN included (one v_ldexp_f64 for the two conversions, the product and
+// the v_rcp_f64 chain of the IEEE division).  Any other product: the division.
+__device__ __forceinline__ bool mean_pow2(int Bmean, int N, int& k) {
+    const long long bn = (long long)Bmean * (long long)N;
+    k = 63 - __builtin_clzll((unsigned long long)(bn | 1));
+    return bn > 0 && (bn & (bn - 1)) == 0;
+}
+__device__ __forceinline__ double var_mean_div(double sumvar, int Bmean, int N) {
+    return sumvar / ((double)Bmean * (double)N);
+}
+__device__ __forceinline__ double var_mean_pow2(double sumvar, int Bmean, int N) {
+    int k;
+    if (mean_pow2(Bmean, N, k)) return __builtin_ldexp(sumvar, -k);
+    return var_mean_div(sumvar, Bmean, N);
+}
+
+// vamp_advance_head for the eight-wave bf16x3 engine's exchange (AMP_X3_W8_XCH): the same record,
+// the mean's quotient through var_mean_pow2; everything after it is vamp_advance_head's.
+__device__ inline VampIter vamp_advance_head_pow2(const VampK& P, const VampIter& cur, const PartAcc& pa, int fixed, int t) {
+    VampIter nx;
+    nx.stopped = 0; nx.T = 0; nx.fixed = fixed; nx.fixed_all = (fixed < 0) ? 1 : 0; nx.G = pa.maxabs;
+    nx.pad1[0] = nx.pad1[1] = nx.pad1[2] = 0.f;
+    nx.vr = nx.alpha = nx.inv1ma = nx.sigma2 = nx.inv_sigma2 = 0.f;
+    if (pa.notclose == 0) {                                              // vamp.py:185-186
+        nx = cur;
+        nx.stopped = 1;
+        nx.T = t + 1;
+        nx.fixed = fixed;
+    } else {
+        const float mean = (float)var_mean_pow2(pa.sumvar, P.Bmean, P.N);
+        const float dxdr = clampf_t(mean / cur.sigma2, AMP_VAR_RATIO_MIN, 1.0f - AMP_VAR_RATIO_MIN);  // vamp.py:85-87
+        const float ns = 1.0f / (1.0f - dxdr);                                                        // vamp.py:89
+        nx.dxdr_prev = dxdr;
+        nx.ns_prev = ns;
+        nx.s2t = clampf_t((cur.sigma2 * dxdr) * ns, AMP_VAR_MIN, AMP_VAR_MAX);                        // vamp.py:92-94
+    }
+    return nx;
+}
+
 // Tail: vamp_lmmse_scalars(first = false) from it.s2t and this lane's s^2.  The four reciprocals
 // are formed unconditionally (no exec-masked region, no wait of its own per term) and added in j
 // order with a select: an invalid term adds +0.0 to a sum that is never -0.0 (it starts at +0.0),

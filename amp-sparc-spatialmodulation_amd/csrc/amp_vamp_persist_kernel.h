@@ -45,6 +45,9 @@ constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iter
 #ifndef AMP_X3_W8_AOP
 #define AMP_X3_W8_AOP 1                 // the eight-wave form's A-operand phases on constants (A/B builds: 0)
 #endif
+#ifndef AMP_X3_W8_XCH
+#define AMP_X3_W8_XCH 1                 // the eight-wave form's exchange reduces its extremes on integer keys (A/B builds: 0)
+#endif
 #ifndef AMP_SCALAR_TAIL
 #define AMP_SCALAR_TAIL 1               // bf16x3 at one workgroup per CU: the LMMSE scalars of vamp_advance inside the
 #endif                                  // next iteration's GEMM1, behind group 0 (A/B builds: 0, the unsplit form)
@@ -155,6 +158,11 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // geometry that N = k = 8 NT NWV fixes as constants, so that plane and row offsets are DS
     // immediates (persist_launch_t checks P against them); the other phases keep the run-time carve
     constexpr bool AOP = X3PF && NWV == 8 && OCC == 1 && AMP_X3_W8_AOP;
+    // the same kernels: the VALU chain around the granule transport (the wave trees of part_publish and
+    // part_gather, thread 0's fold over the waves, the gather's lane fold) takes the two extremes as
+    // integer keys and the mean's quotient by a power of two as a scaling (amp_persist.h
+    // part_publish_keys / part_gather_keys, amp_vamp.h vamp_advance_head_pow2); same bits
+    constexpr bool XCH = X3PF && NWV == 8 && OCC == 1 && AMP_X3_W8_XCH;
     constexpr int CN = 8 * NT * NWV;
     constexpr AopLayout CY = aop_layout(CN);
 #define c64 (static_cast<const Const64&>(*Dp))
@@ -362,7 +370,11 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
             S2Lane s2x;
             if constexpr (STAIL == 0) s2x = s2_lane(P, P.s + (size_t)ep * P.sch);
             const unsigned tag = P.gen * (unsigned)(P.max_iter + 1) + (unsigned)te + 1u;
-            if (!part_gather(grs, ((unsigned)te * nwx + wg0) * 32u, P.wpe, tag, P.pbar + 1, g, scr, &s_flag)) return false;
+            if constexpr (XCH) {
+                if (!part_gather_keys(grs, ((unsigned)te * nwx + wg0) * 32u, P.wpe, tag, P.pbar + 1, g, scr, &s_flag)) return false;
+            } else {
+                if (!part_gather(grs, ((unsigned)te * nwx + wg0) * 32u, P.wpe, tag, P.pbar + 1, g, scr, &s_flag)) return false;
+            }
             stamp(te, 6);
             fixed = 0;
             if (part_allnan(g)) {
@@ -443,7 +455,9 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 fixed = (int)c;
             }
         if constexpr (STAIL != 0) {
-            nx = vamp_advance_head(P, cur, g, fixed, te);   // (slot 9: the tail's end, in iteration te + 1)
+            // (slot 9: the tail's end, in iteration te + 1)
+            if constexpr (XCH) nx = vamp_advance_head_pow2(P, cur, g, fixed, te);
+            else nx = vamp_advance_head(P, cur, g, fixed, te);
         } else {
             stamp(te, 9);   // (slot 9: vamp_advance starts)
             nx = vamp_advance(P, cur, g, fixed, te, scr, &s2x);
@@ -856,7 +870,8 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
             denoise_sections_u<true, KK, DU, PKDEN, DENFAST>(pol, nrows * spr, M, P.c, pa);   // two waves per SIMD: scalar f32 (amp_denoise.h)
         stamp(t, 8);
         const unsigned tag = P.gen * (unsigned)(P.max_iter + 1) + (unsigned)t + 1u;   // never 0 mod 2^32 in practice
-        part_publish(pa, grs, ((unsigned)t * nwx + wgx) * 32u, tag, scr);
+        if constexpr (XCH) part_publish_keys<NWV>(pa, grs, ((unsigned)t * nwx + wgx) * 32u, tag, scr);
+        else part_publish(pa, grs, ((unsigned)t * nwx + wgx) * 32u, tag, scr);
         if (P.dump) {   // xmmse and var after the denoiser (part_publish's barrier ordered the LDS writes)
             float* dp = P.dump + (((size_t)t * nwg + wg) * 5 + 2) * PBM * twoN;
             for (int e = tid; e < PBM * twoN; e += PWG) dp[e] = sX[(e / twoN) * ldr + e % twoN];

@@ -364,3 +364,71 @@ int amp_x3_planes_debug(const void* rows, int32_t nrows, void* planes, void* str
     AMP_LAUNCH_CHECK("amp_x3_planes_debug");
     return AMP_OK;
 }
+
+// Diagnostic (amp_exchange_reduce_debug): the reduction chain of vamp_persist's exchange on
+// caller-supplied values, today's forms and the key forms of the eight-wave bf16x3 kernel side by
+// side.  One workgroup of eight waves: part_publish and part_publish_keys on one PartAcc per thread
+// (the granules land in `out`, the waves' Partials are copied from the scratch), part_gather and
+// part_gather_keys on up to 256 granule pairs (the kernel stamps the tag it then sweeps for into a
+// staging copy, so the sweep passes at once), and the mean's quotient in both forms per thread.
+namespace amp {
+
+constexpr int XRD_WG = 512, XRD_MAXG = 256;
+constexpr unsigned XRD_PUB = 0, XRD_WAVES = 64, XRD_GATHER = 576, XRD_FLAGS = 640, XRD_MEAN = 672,
+                   XRD_STAGE = XRD_MEAN + 2 * XRD_WG * 8, XRD_BYTES = XRD_STAGE + XRD_MAXG * 32;
+
+__global__ __launch_bounds__(XRD_WG) void exchange_reduce_debug_kernel(const Partial* __restrict__ vals,
+                                                                        const u32x4* __restrict__ grans, int ngran,
+                                                                        const double* __restrict__ sums,
+                                                                        const int2* __restrict__ divs, unsigned* out) {
+    __shared__ __attribute__((aligned(16))) unsigned scr[256];
+    __shared__ int s_flag;
+    const int tid = threadIdx.x;
+    const unsigned tag = 1u;
+    u32x4* stage = reinterpret_cast<u32x4*>(reinterpret_cast<char*>(out) + XRD_STAGE);
+    if (tid < XRD_MAXG) {
+        u32x4 a = {0u, 0u, 0u, 0u}, b = a;
+        if (tid < ngran) { a = grans[2 * tid]; b = grans[2 * tid + 1]; a.w = tag; b.w = tag; }
+        stage[2 * tid] = a; stage[2 * tid + 1] = b;
+    }
+    if (tid < 8) out[XRD_FLAGS / 4 + tid] = 0u;
+    __threadfence();
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t ors = gran_rsrc(out, XRD_BYTES);
+    const __amdgpu_buffer_rsrc_t srs = gran_rsrc(stage, XRD_MAXG * 32);
+    PartAcc p;
+    p.sumvar = vals[tid].sumvar; p.maxabs = vals[tid].maxabs; p.minsecmax = vals[tid].minsecmax; p.notclose = vals[tid].notclose;
+    for (int form = 0; form < 2; ++form) {
+        if (form == 0) part_publish(p, ors, XRD_PUB, 0u, scr);
+        else part_publish_keys<XRD_WG / 64>(p, ors, XRD_PUB + 32, 0u, scr);
+        if (tid < 64) out[(XRD_WAVES + 256 * form) / 4 + tid] = scr[tid];   // the eight waves' Partials
+        __syncthreads();
+    }
+    for (int form = 0; form < 2; ++form) {
+        PartAcc g;
+        const bool ok = form == 0 ? part_gather(srs, 0u, ngran, tag, out + XRD_FLAGS / 4, g, scr, &s_flag)
+                                  : part_gather_keys(srs, 0u, ngran, tag, out + XRD_FLAGS / 4, g, scr, &s_flag);
+        if (tid == 0) {
+            Partial o;
+            o.sumvar = g.sumvar; o.maxabs = g.maxabs; o.minsecmax = g.minsecmax; o.notclose = g.notclose;
+            o.pad = ok ? 1u : 0u;
+            *reinterpret_cast<Partial*>(reinterpret_cast<char*>(out) + XRD_GATHER + 32 * form) = o;
+        }
+    }
+    double* mean = reinterpret_cast<double*>(reinterpret_cast<char*>(out) + XRD_MEAN);
+    mean[tid] = var_mean_div(sums[tid], divs[tid].x, divs[tid].y);
+    mean[XRD_WG + tid] = var_mean_pow2(sums[tid], divs[tid].x, divs[tid].y);
+}
+
+}  // namespace amp
+
+int amp_exchange_reduce_debug(const void* vals, const void* grans, int32_t ngran, const void* sums, const void* divs,
+                              void* out, void* stream) {
+    using namespace amp;
+    AMP_REQUIRE(vals && grans && sums && divs && out, "amp_exchange_reduce_debug: null pointer argument");
+    AMP_REQUIRE(ngran >= 1 && ngran <= XRD_MAXG, "amp_exchange_reduce_debug: ngran = %d (1 ... %d)", ngran, XRD_MAXG);
+    hipLaunchKernelGGL(exchange_reduce_debug_kernel, dim3(1), dim3(XRD_WG), 0, (hipStream_t)stream, (const Partial*)vals,
+                       (const u32x4*)grans, (int)ngran, (const double*)sums, (const int2*)divs, (unsigned*)out);
+    AMP_LAUNCH_CHECK("amp_exchange_reduce_debug");
+    return AMP_OK;
+}

@@ -501,6 +501,22 @@ int amp_decide_debug_sections(const amp_dims* d, const amp_constellation* c, con
  * column j ^ 8 (r & 15)): form 0 the shared row-item writer (x3_store8), 1 the eight-wave engine's
  * item form of it, 2 the shared accumulator-layout writer (x3_store_acc), 3 its item form. */
 int amp_x3_planes_debug(const void* rows, int32_t nrows, void* planes, void* stream);
+/* Diagnostic: the reduction chain of the persistent VAMP engine's per-iteration exchange on
+ * caller-supplied values, in one workgroup of eight waves: the shared forms (float64 NaN-propagating
+ * extremes, the IEEE division of the mean) and the eight-wave bf16x3 kernel's forms (extremes on
+ * integer keys, the quotient by a power of two as a scaling) side by side.
+ *   vals   [512] x {float64 sumvar, float64 maxabs, float64 minsecmax, uint32 notclose, uint32 0}: one
+ *          record per thread, as the denoiser leaves them (maxabs / minsecmax float32-exact or NaN);
+ *   grans  [ngran][8] uint32, 1 <= ngran <= 256: granule pairs as the workgroups publish them
+ *          ({sumvar lo, hi, notclose, tag}, {maxabs f32, minsecmax f32, 0, tag}; the tags are ignored);
+ *   sums   [512] float64 and divs [512][2] int32 (Bmean, N): the mean's quotient per thread;
+ *   out    17056 bytes: at 0 the two granules of the shared publish (tag 0), at 32 the key form's; at
+ *          64 the eight waves' records of the shared wave tree (the vals layout), at 320 the key
+ *          form's; at 576 the gathered record of the shared form (the vals layout, last word 1: the
+ *          sweep completed), at 608 the key form's; at 640 the abort word (0); at 672 [512] float64
+ *          quotients of the division, at 4768 of the scaling form; from 8864 on scratch. */
+int amp_exchange_reduce_debug(const void* vals, const void* grans, int32_t ngran, const void* sums, const void* divs,
+                              void* out, void* stream);
 /* Same counters with Loss.random_decision (loss.py:252-280, generator_mode='random'): per
  * channel use the Na largest |x_m| (NaN largest; exact ties by larger index), each decided to
  * its nearest point, compared in ascending position order with the row's true sorted indices.

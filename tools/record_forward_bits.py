@@ -3,8 +3,8 @@
 tests/test_gpu_vamp_ring_prefill.py (tests/golden/ring_prefill_bits.part<k>.npz).
 
   python tools/record_forward_bits.py [--out DIR] [--stem STEM] [--cases "Nt,Na,Nr,B,alphabet;..."] [--share-channel]
-                                      [--ebn0 "dB;..."] [--nan-row "row;..."] [--inf-entry "row,col;..."] [--dump]
-                                      [--dump-wr]
+                                      [--ebn0 "dB;..."] [--nan-row "row;..."] [--inf-entry "row,col;..."]
+                                      [--scale-y "f;..."] [--dump] [--dump-wr]
 
 --stem / --cases record another fixture (tests/golden/<stem>.part<k>.npz) for another case list;
 --share-channel draws one channel, the first case's, stores it once ('shared/U', 's', 'Vh', 'SNR')
@@ -13,6 +13,8 @@ and runs every case that agrees with it in Nt and Nr on it (another case draws a
 stores that case's SNR as '<case>/SNR', e.g. to record a forward that stops before the cap;
 --nan-row sets one row of y to NaN per case (an empty entry: none), in both forwards;
 --inf-entry sets one entry of y to +inf per case ("row,col"; an empty entry: none), in both forwards;
+--scale-y multiplies y of a case by f (an empty entry: 1), in both forwards, with the noise variance left
+at the channel's: the logits grow with f, which drives a case into the exact-float64 rare path;
 --dump-wr runs both forwards with the state dump on and stores each forward's GEMM1 epilogue w and
 GEMM2 epilogue r per iteration: the first WR_FULL iterations whole ('f<i>_it_w', 'f<i>_it_r'
 [WR_FULL, B, 2N]), every iteration as one CRC-32 per trial row ('f<i>_it_wcrc', 'f<i>_it_rcrc' [T, B])
@@ -58,11 +60,12 @@ def config(Nt, Na, Nr, B, alphabet, device):
                   channel_profile='uniform', channel_truncation='tail', device=device)
 
 
-def make_inputs(case, shared=None, ebn0=None, nan_row=None, inf_entry=None):
+def make_inputs(case, shared=None, ebn0=None, nan_row=None, inf_entry=None, scale_y=None):
     """One channel and two epochs of messages + noise (host tensors), in the reference's call order.
     shared: the make_inputs result of another case whose channel (A, U, s, Vh, SNR) this one uses;
     ebn0: this case's own Eb/N0 (else the alphabet's default, or the shared channel's SNR);
-    nan_row: the row of y set to NaN in both epochs; inf_entry: the (row, column) of y set to +inf in both."""
+    nan_row: the row of y set to NaN in both epochs; inf_entry: the (row, column) of y set to +inf in both;
+    scale_y: the factor y is multiplied by in both (before nan_row / inf_entry)."""
     from channel import Channel
     from data import Data
     np.random.seed(SEED)
@@ -81,6 +84,8 @@ def make_inputs(case, shared=None, ebn0=None, nan_row=None, inf_entry=None):
     for _ in range(2):
         x, sym, idx = da.generate_message()
         y = A @ x + ch.awgn(SNR)
+        if scale_y is not None:
+            y = y * scale_y
         if nan_row is not None:
             y[nan_row] = float('nan')
         if inf_entry is not None:
@@ -101,7 +106,7 @@ def forward(det, chan, SNR, ep, device):
     out = dict(r=torch.view_as_real(det.last.r.squeeze(-1).contiguous()).cpu().numpy().copy(),
                xmmse=torch.view_as_real(det.last.xmmse.squeeze(-1).contiguous()).cpu().numpy().copy(),
                var=det.last.var.squeeze(-1).cpu().numpy().copy(),
-               T=np.array([int(L.last_status.T)]), counts=np.asarray(counts_to_vector(L.last_counts)))
+               T=np.array([int(L.last_status.T)]), nan_state=np.array([int(L.last_status.nan_state)]), counts=np.asarray(counts_to_vector(L.last_counts)))
     return (b1 - b0, r1 - r0), out
 
 
@@ -216,6 +221,7 @@ def main():
     ap.add_argument('--ebn0', default=None, help='"dB;..." per case (one value: every case; empty: the default)')
     ap.add_argument('--nan-row', default=None, help='"row;..." per case: that row of y is NaN (empty: none)')
     ap.add_argument('--inf-entry', default=None, help='"row,col;..." per case: that entry of y is +inf (empty: none)')
+    ap.add_argument('--scale-y', default=None, help='"f;..." per case: y is multiplied by f (empty: 1)')
     ap.add_argument('--dump-wr', action='store_true', help="both forwards' per-iteration w and r (see above)")
     ap.add_argument('--dump', action='store_true', help="the reuse forward's per-iteration var, wave sums and exchange records")
     args = ap.parse_args()
@@ -237,16 +243,21 @@ def main():
         vals = args.inf_entry.split(';')
         assert len(vals) == len(cases), (vals, cases)
         inf_entries = [tuple(int(u) for u in v.split(',')) if v.strip() else None for v in vals]
+    scales = [None] * len(cases)
+    if args.scale_y is not None:
+        vals = args.scale_y.split(';')
+        assert len(vals) == len(cases), (vals, cases)
+        scales = [float(v) if v.strip() else None for v in vals]
     device = torch.device('cuda', 0)
     flat = {}
     shared = None
-    for case, eb, nr, ie in zip(cases, ebn0, nan_rows, inf_entries):
+    for case, eb, nr, ie, sc in zip(cases, ebn0, nan_rows, inf_entries, scales):
         name = case_name(*case)
         own = shared is not None and case[0:3:2] != shared['dims']   # another Nt, Nr: its own channel
-        inp = make_inputs(case, None if own else shared, eb, nr, ie)
+        inp = make_inputs(case, None if own else shared, eb, nr, ie, sc)
         res = run_case(case, inp, device, args.dump, args.dump_wr)
         print(name, 'prepares (building, reuse) per forward:', [m for m, _ in res],
-              'T:', [int(o['T'][0]) for _, o in res])
+              'T:', [int(o['T'][0]) for _, o in res], 'nan_state:', [int(o['nan_state'][0]) for _, o in res])
         if args.share_channel and shared is None:
             shared = dict(inp, dims=case[0:3:2])
         chan = 'shared' if args.share_channel and not own else name

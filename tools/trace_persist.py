@@ -21,7 +21,11 @@ import torch        # noqa: E402
 
 PHASES = ['r~ build', 'GEMM1', 'w store', 'GEMM2 + r', 'denoiser', 'partial publish', 'partial gather', 'scalars']
 STRIDE = 10   # stamps per (workgroup, iteration): amp_vamp_persist.hip AMP_TRACE_STRIDE
-ORDER = [0, 1, 2, 3, 4, 8, 5, 6, 7]   # stamp slots in time order
+# stamp slots in time order.  The exchange's three phases: slot 8 (this wave's denoiser done) -> 5 is the
+# partial publish (wave tree, both barriers, thread 0's fold and granule stores: it waits for the SIMD's
+# partner wave), 5 -> 6 the gather (sweep, lane fold, tree, LDS broadcast), 6 -> 7 the scalars (the all-NaN
+# and danger tests, then vamp_advance or its head)
+ORDER = [0, 1, 2, 3, 4, 8, 5, 6, 7]
 SPHASES = ['scalars + x planes', 'GEMM1', 's store', 'GEMM2 + xmap', 'denoiser', 'psi + publish',
            'partial gather', 'danger / exit']
 SORDER = [0, 1, 2, 3, 4, 5, 6, 7, 8]
