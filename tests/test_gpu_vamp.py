@@ -335,7 +335,8 @@ def test_vamp_x3_gemm_matches_f32(device, name, iters):
     """The split-precision persistent GEMMs (bf16x3 and fp16x2) against the f32-MFMA ones, all
     measured against the numpy oracle (f32 BLAS GEMMs in yet another summation order): after 1
     and 3 iterations r of each split engine is as close to the oracle as the f32 engine's
-    (tolerance: 4x the f32 engine's own deviation, floored at 2e-6 of max|r|)."""
+    (tolerance: 4x the f32 engine's own deviation, floored at 2e-6 of max|r|).
+    The absolute check of these GEMMs (float64, per iteration and phase) is test_gpu_persist_linear.py."""
     from vamp import VAMP
     import amp_native as nat
     ent = CURVES[name]
