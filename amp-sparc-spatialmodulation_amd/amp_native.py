@@ -157,6 +157,8 @@ SIGNATURES = {
     'amp_scamp_trials_ch_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I]),
     'amp_scamp_trials_ch_run': (C.c_int, [_D, _K, C.POINTER(AmpScampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _I,
                                           _P]),
+    'amp_vamp_trials_ch_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I, _I]),
+    'amp_vamp_trials_ch_run': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _I, _P]),
     'amp_bamp_workspace_bytes': (C.c_size_t, [_D, _I]),
     'amp_bamp_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),
     'amp_bamp_prepare': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),

@@ -17,6 +17,12 @@
 // stopped returns at once, and every kernel returns at once when the stop counter has reached E.
 // A row's GEMM result does not depend on the other rows of its tile (each MFMA output row reduces
 // its own A row only), so a trial's values are those of its own B = 1 forward on the launch engine.
+// amp_vamp_trials_ch_run: the same over G channels, trial e on channel e / per_channel
+// (vamp_model.py:45-61 redraws the channel every `res` epochs).  The channel forms tvamp_k1_ch /
+// tvamp_k2_ch / tvamp_r_ch take the channel's view of the parameter block at their entry (Wt1, Wt2,
+// s, s2 and the channel's last row as the row limit) and call the same bodies; y~ is gemm_store_ch
+// with each channel's Wt0, the iteration-0 record is one per channel, and the operators of all
+// channels are packed in three launches.
 #include <algorithm>
 #include <mutex>
 
@@ -33,15 +39,21 @@ struct TVampWs {
     size_t bytes;
 };
 
-static TVampWs tvamp_carve(const amp_dims* d, int k, int E, void* base) {
+// floats between two channels' s2 in a workspace of G channels: whole 256-byte granules, so G
+// channels cost exactly G times one channel's bytes (one channel: the dense k of amp_vamp_trials_run)
+inline size_t tvamp_s2_stride(int k, int G) { return G == 1 ? (size_t)k : (size_t)round_up(k, 64); }
+
+// G: channels whose packed operators and s2 the workspace holds (amp_vamp_trials_ch_run; one
+// channel: the layout and bytes of amp_vamp_trials_run)
+static TVampWs tvamp_carve(const amp_dims* d, int k, int E, void* base, int G = 1) {
     VampK P;
     vamp_geometry(d, k, P);
     Carve cv(base);
     TVampWs w;
-    w.Wt0 = cv.take<float>((size_t)P.ncp0 * P.kap0);
-    w.Wt1 = cv.take<float>((size_t)P.ncp1 * P.kap1);
-    w.Wt2 = cv.take<float>((size_t)P.ncp2 * P.kap2);
-    w.s2 = cv.take<float>((size_t)k);
+    w.Wt0 = cv.take<float>((size_t)G * P.ncp0 * P.kap0);
+    w.Wt1 = cv.take<float>((size_t)G * P.ncp1 * P.kap1);
+    w.Wt2 = cv.take<float>((size_t)G * P.ncp2 * P.kap2);
+    w.s2 = cv.take<float>((size_t)G * tvamp_s2_stride(k, G));
     w.ytil = cv.take<float>((size_t)E * 2 * k);
     w.w = cv.take<float>((size_t)E * P.wld);
     w.var1 = cv.take<float>((size_t)E * d->N);
@@ -126,6 +138,108 @@ __global__ __launch_bounds__(RWG) void tvamp_r(VampK PE, Const64 c64, int t, uns
     if (threadIdx.x == 0 && nx.stopped) __hip_atomic_fetch_add(nstop, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- the channel forms (amp_vamp_trials_ch_run): row tile rb belongs to channel rb / tpg
+// (amp_trials.h channel_tile).  CH.wstride: floats between two channels' Wt0 / Wt1 / Wt2 / s2; the
+// singular values lie dense, k apart.  A kernel takes the channel's view of its by-value P at the
+// entry and runs the one-channel kernel's calls: a row has the bits of its own B = 1 forward with
+// that channel, wherever in a tile it lies (every row stride is even: no alignment changes with a
+// first row that is no multiple of 32, or odd). ----
+
+// false (workgroup-uniform) when every trial has stopped or no row of the tile is live; else s_it
+// holds the tile's records (rows of the next channel as stopped) and P is channel ct.g's: its
+// operators and s2, and its last row + 1 as the row limit of the loaders and epilogues (P.B)
+__device__ __forceinline__ bool tvamp_ch_enter(VampK& P, const TrialChannels& CH, const ChannelTile& ct,
+                                               const unsigned* nstop, VampIter* s_it) {
+    if (*nstop >= (unsigned)P.B) return false;
+    if (!vamp_tile_records(P.iters, ct.row0, ct.lim, s_it)) return false;
+    P.Wt1 += (size_t)ct.g * CH.wstride[1];
+    P.Wt2 += (size_t)ct.g * CH.wstride[2];
+    P.s2 += (size_t)ct.g * CH.wstride[3];
+    P.s += (size_t)ct.g * P.k;
+    P.B = ct.lim;
+    return true;
+}
+
+__global__ __launch_bounds__(AMP_WG) void tvamp_k1_ch(VampK P, TrialChannels CH, const unsigned* nstop) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ VampIter s_it[GBM];
+    const GemmTile tile = xcd_tile();
+    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const int row0 = ct.row0, col0 = tile.cb * 128;
+    if (!tvamp_ch_enter(P, CH, ct, nstop, s_it)) return;
+    const VampLiveRows g{s_it};
+    gemm_tile<128>(vamp_aload_rt(P, g, row0), P.Wt1, P.kap1, row0, col0, lds);
+    vamp_lmmse_epilogue(P, g, lds, row0, col0);
+}
+
+template <int BN, int KK>
+__global__ __launch_bounds__(AMP_WG) void tvamp_k2_ch(VampK P, TrialChannels CH, int t, const unsigned* nstop) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ VampIter s_it[GBM];
+    const GemmTile tile = xcd_tile();
+    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const int row0 = ct.row0, col0 = tile.cb * BN;
+    if (!tvamp_ch_enter(P, CH, ct, nstop, s_it)) return;
+    const VampLiveRows g{s_it};
+    gemm_tile<BN>(ALoadPlain{P.w, P.wld, ct.lim, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
+    const int nrows = min(GBM, ct.lim - row0), ncols = min(BN, 2 * P.N - col0);
+    vamp_r_epilogue<BN>(P, g, lds, row0, col0, nrows, ncols);
+    const int nct = P.ncp2 / BN, slot = seq_part_slot(tile.cb, nct);
+    for (int rho = 0; rho < nrows; ++rho) {
+        if (!g.live(rho)) continue;   // workgroup-uniform
+        const VampDenoisePolicy pol = vamp_policy<BN>(P, g, t, lds, row0, col0, ncols, rho);
+        PartAcc pa;
+        denoise_sections<true, KK>(pol, pol.spr, P.M, P.c, pa);
+        part_block_store(pa, P.parts + (size_t)(row0 + rho) * nct + slot, lds + GemmCfg<BN>::CTILE_FLOATS);
+    }
+}
+struct TVampK2Ch {
+    template <int BN, int KK>
+    static constexpr auto fn() { return &tvamp_k2_ch<BN, KK>; }
+};
+
+// tvamp_r with trial e's channel: P.s at channel e / per's singular values (vamp_lmmse_scalars'
+// mean(scale), vamp.py:68-71)
+__global__ __launch_bounds__(RWG) void tvamp_r_ch(VampK PE, int per, Const64 c64, int t, unsigned* nstop) {
+    __shared__ __attribute__((aligned(16))) float lds[512];
+    if (*nstop >= (unsigned)PE.B) return;
+    const int e = blockIdx.x;
+    const VampIter cur = PE.iters[e];
+    if (cur.stopped) return;
+    VampK P = PE;
+    const int nct = PE.ncp2 / PE.bn2;
+    P.B = 1; P.Bmean = 1;
+    P.s = PE.s + (size_t)(e / per) * PE.k;
+    P.r = PE.r + (size_t)e * 2 * PE.N; P.xm = PE.xm + (size_t)e * 2 * PE.N;
+    P.var0 = PE.var0 + (size_t)e * PE.N; P.var1 = PE.var1 + (size_t)e * PE.N;
+    P.secmax = PE.secmax + (size_t)e * PE.L; P.secabs = PE.secabs + (size_t)e * PE.L;
+    P.parts = PE.parts + (size_t)e * nct;
+    const VampIter nx = vamp_reduce(P, c64, cur, P.parts, nct, &PE.iters[e], &PE.status[e], t, lds);
+    if (threadIdx.x == 0 && nx.stopped) __hip_atomic_fetch_add(nstop, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// tvamp_init_kernel for G channels: every channel's s2 and its own iteration-0 record
+// (vamp_first_iter sums 1 / (s_i^2 + vr) over the channel's singular values), written to the
+// channel's trials; the channels go grid-strided over the workgroups
+__global__ __launch_bounds__(256) void tvamp_init_ch_kernel(VampK P, TrialChannels CH, int G, unsigned* nstop) {
+    __shared__ __attribute__((aligned(16))) float lds[64];
+    vamp_init_state(P);   // and channel 0's s2
+    const size_t rest = (size_t)(G - 1) * P.k;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < rest; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t g = 1 + i / P.k, o = i % P.k;
+        const float sv = P.s[g * P.k + o];
+        P.s2[g * CH.wstride[3] + o] = sv * sv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *nstop = 0u;
+    for (int g = blockIdx.x; g < G; g += gridDim.x) {   // workgroup-uniform
+        VampK Pg = P;
+        Pg.s = P.s + (size_t)g * P.k;
+        const VampIter it = vamp_first_iter(Pg, lds);
+        const int lim = min((g + 1) * CH.per, P.B);
+        for (int e = g * CH.per + threadIdx.x; e < lim; e += blockDim.x) P.iters[e] = it;
+    }
+}
+
 // Trial e's last executed iteration wrote var into buffer (T_e - 1) & 1; buffer 0 is the caller's.
 __global__ __launch_bounds__(256) void tvamp_output_kernel(VampK P) {
     const int e = blockIdx.x;
@@ -143,6 +257,45 @@ static int tvamp_attrs() {
         g_tvamp_attr_rc = rc ? rc : vamp_k2_attrs<TVampK2>();
     });
     return g_tvamp_attr_rc;
+}
+
+static std::once_flag g_tvamp_ch_attr_once;
+static int g_tvamp_ch_attr_rc = 0;
+
+static int tvamp_ch_attrs() {
+    std::call_once(g_tvamp_ch_attr_once, [] {
+        const int rc = set_lds_attr<128>((const void*)tvamp_k1_ch);
+        g_tvamp_ch_attr_rc = rc ? rc : vamp_k2_attrs<TVampK2Ch>();
+    });
+    return g_tvamp_ch_attr_rc;
+}
+
+// vamp_k2_launch over gr = G * tpg row tiles
+static void tvamp_k2_ch_launch(const VampK& P, const TrialChannels& CH, int gr, int t, const unsigned* nstop,
+                               hipStream_t st) {
+    const dim3 g2(gr, P.ncp2 / P.bn2);
+    dispatch_K(P.c.K, [&](auto kk) {
+        constexpr int KK = decltype(kk)::value;
+        if (P.bn2 == 128)
+            hipLaunchKernelGGL((tvamp_k2_ch<128, KK>), g2, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, CH, t, nstop);
+        else
+            hipLaunchKernelGGL((tvamp_k2_ch<256, KK>), g2, dim3(AMP_WG), GemmCfg<256>::LDS_BYTES, st, P, CH, t, nstop);
+    });
+}
+
+// vamp_pack_f32 for G channels (a->U c64 [G][n][k], a->s f32 [G][k], a->Vh c64 [G][k][N]), each
+// channel's Wt0 scaled by its own singular values: three launches, whatever G
+static int vamp_pack_f32_ch(const VampK& P, const TrialChannels& CH, const amp_vamp_args* a, int G, hipStream_t st) {
+    int rc;
+    const size_t su = (size_t)P.n * P.k, sv = (size_t)P.k * P.N;
+    if ((rc = build_cweight_ch((const float2*)a->U, su, 1, P.k, 1, P.k, P.n, (float*)P.Wt0, CH.wstride[0], P.kap0,
+                               P.ncp0, G, st, P.s, (size_t)P.k)))
+        return rc;
+    if ((rc = build_cweight_ch((const float2*)a->Vh, sv, P.N, 1, 0, P.k, P.N, (float*)P.Wt1, CH.wstride[1], P.kap1,
+                               P.ncp1, G, st)))
+        return rc;
+    return build_cweight_ch((const float2*)a->Vh, sv, 1, P.N, 1, P.N, P.k, (float*)P.Wt2, CH.wstride[2], P.kap2, P.ncp2,
+                            G, st);
 }
 
 }  // namespace amp
@@ -210,6 +363,87 @@ int amp_vamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp
         AMP_LAUNCH_CHECK("tvamp_k2");
         hipLaunchKernelGGL(tvamp_r, dim3(E), dim3(RWG), 0, st, P, c64, t, w.nstop);
         AMP_LAUNCH_CHECK("tvamp_r");
+    }
+    hipLaunchKernelGGL(tvamp_output_kernel, dim3(E), dim3(256), 0, st, P);
+    AMP_LAUNCH_CHECK("tvamp_output");
+    return dec ? trials_decide_launch(d, c, td, E, w.dec, st) : AMP_OK;
+}
+
+size_t amp_vamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t k, int32_t max_iter, int32_t trials,
+                                          int32_t per_channel) {
+    if (!d || k <= 0 || max_iter <= 0 || trials <= 0 || per_channel < 1 || d->B != 1) return 0;
+    if (d->N <= 0 || d->n <= 0 || d->M <= 0 || d->N % 2 != 0 || k > d->N || k > d->n || !vamp_index_ok(d, trials))
+        return 0;
+    int per = per_channel;
+    const int G = trial_channels(trials, per);
+    if (G > WCH_MAX) return 0;
+    return tvamp_carve(d, k, trials, nullptr, G).bytes;
+}
+
+int amp_vamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
+                           const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
+    int rc = check_dims(d, c, true, true);   // any n, any k, any even N, a partial last column tile (amp_vamp_run)
+    if (rc) return rc;
+    AMP_REQUIRE(d->B == 1, "amp_vamp_trials_ch_run: dims describe ONE trial (B = %d, must be 1)", d->B);
+    AMP_REQUIRE(trials >= 1, "amp_vamp_trials_ch_run: trials = %d", trials);
+    AMP_REQUIRE(per_channel >= 1, "amp_vamp_trials_ch_run: per_channel = %d", per_channel);
+    AMP_REQUIRE(vamp_index_ok(d, trials), "amp_vamp_trials_ch_run: %d trials of max(2N, 2n) = %d columns need more "
+                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
+    const int E = trials;
+    int per = per_channel;
+    const int G = trial_channels(E, per);
+    AMP_REQUIRE(G <= WCH_MAX, "amp_vamp_trials_ch_run: %d channels (at most %d per call: a grid axis)", G, WCH_MAX);
+    AMP_REQUIRE(a && a->U && a->s && a->Vh && a->y && a->r && a->xmmse && a->var && a->status && a->ws,
+                "amp_vamp_trials_ch_run: null pointer argument");
+    AMP_REQUIRE(a->k > 0 && a->k <= d->N && a->k <= d->n, "amp_vamp_trials_ch_run: k = %d must be min(n, N)", a->k);
+    AMP_REQUIRE(a->max_iter > 0, "amp_vamp_trials_ch_run: max_iter must be positive");
+    AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES,
+                "amp_vamp_trials_ch_run: the persistent engine has no independent-trial form");
+    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32,
+                "amp_vamp_trials_ch_run: f32 GEMMs only (gemm %d)", a->gemm);
+    const TVampWs w = tvamp_carve(d, a->k, E, a->ws, G);
+    AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_vamp_trials_ch_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
+    TrialsDecide td{};
+    if (dec && (rc = trials_decide_args(d, dec, a->r, a->xmmse, td))) return rc;
+    VampK P{};
+    vamp_geometry(d, a->k, P);
+    P.B = E;            // rows; every per-trial quantity is formed over one row (tvamp_r_ch: Bmean = 1)
+    P.Bmean = 1;
+    P.max_iter = a->max_iter;
+    P.noise_var = a->noise_var;
+    P.sparsity = a->sparsity;
+    P.Wt0 = w.Wt0; P.Wt1 = w.Wt1; P.Wt2 = w.Wt2;   // channel 0's, as s and s2; the kernels step to theirs
+    P.s = (const float*)a->s; P.s2 = w.s2; P.ytil = w.ytil; P.w = w.w;
+    P.r = (float*)a->r; P.xm = (float*)a->xmmse;
+    P.var0 = (float*)a->var; P.var1 = w.var1;
+    P.secmax = w.secmax; P.secabs = w.secabs; P.parts = w.parts; P.iters = w.iters;
+    P.status = (amp_status*)a->status;
+    P.y = (const float*)a->y;
+    P.x3 = 0;           // amp_status.gemm = AMP_ARITH_F32
+    P.c = to_const(c);
+    TrialChannels CH{};
+    CH.per = per; CH.tpg = cdiv(per, GBM);
+    CH.wstride[0] = (size_t)P.ncp0 * P.kap0; CH.wstride[1] = (size_t)P.ncp1 * P.kap1;
+    CH.wstride[2] = (size_t)P.ncp2 * P.kap2; CH.wstride[3] = tvamp_s2_stride(P.k, G);
+    const Const64 c64 = to_const64(c);
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = tvamp_ch_attrs())) return rc;
+    if ((rc = vamp_pack_f32_ch(P, CH, a, G, st))) return rc;   // every channel's operators, once per call
+    const int gi = (int)std::min<size_t>(((size_t)E * P.N + 255) / 256, 2048);
+    hipLaunchKernelGGL(tvamp_init_ch_kernel, dim3(gi), dim3(256), 0, st, P, CH, G, w.nstop);
+    AMP_LAUNCH_CHECK("tvamp_init_ch");
+    rc = gemm_store_ch((const float*)a->y, 2 * P.n, E, 2 * P.n, P.Wt0, CH.wstride[0], P.kap0, P.ncp0, P.ytil, 2 * P.k,
+                       2 * P.k, per, CH.tpg, G, st);
+    if (rc) return rc;
+    const int gr = G * CH.tpg;                     // <= E row tiles
+    const dim3 g1(gr, P.ncp1 / 128);
+    for (int t = 0; t < P.max_iter; ++t) {
+        hipLaunchKernelGGL(tvamp_k1_ch, g1, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, CH, (const unsigned*)w.nstop);
+        AMP_LAUNCH_CHECK("tvamp_k1_ch");
+        tvamp_k2_ch_launch(P, CH, gr, t, (const unsigned*)w.nstop, st);
+        AMP_LAUNCH_CHECK("tvamp_k2_ch");
+        hipLaunchKernelGGL(tvamp_r_ch, dim3(E), dim3(RWG), 0, st, P, per, c64, t, w.nstop);
+        AMP_LAUNCH_CHECK("tvamp_r_ch");
     }
     hipLaunchKernelGGL(tvamp_output_kernel, dim3(E), dim3(256), 0, st, P);
     AMP_LAUNCH_CHECK("tvamp_output");

@@ -12,6 +12,7 @@
 #include "amp_host.h"
 #include "amp_gemm_h2.h"
 #include "amp_persist.h"
+#include "amp_trials.h"
 
 namespace amp {
 
@@ -437,9 +438,11 @@ int weight_kband(const float* wp, int kap, int ncp, int BN, int* band, hipStream
 // channel alone gives. ----
 
 __global__ void build_cweight_ch_kernel(const float2* __restrict__ src, size_t sg, long so, long sj, int conj, int O,
-                                        int J, float* __restrict__ wt, size_t dg, int kap, int ncp) {
+                                        int J, float* __restrict__ wt, size_t dg, int kap, int ncp,
+                                        const float* __restrict__ rowscale, size_t rs) {
     src += (size_t)blockIdx.y * sg;
     wt += (size_t)blockIdx.y * dg;
+    if (rowscale) rowscale += (size_t)blockIdx.y * rs;
     const long total = (long)(ncp / 2) * (kap / 2);
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int o = (int)(e / (kap / 2)), j = (int)(e % (kap / 2));
@@ -448,6 +451,11 @@ __global__ void build_cweight_ch_kernel(const float2* __restrict__ src, size_t s
             const float2 v = src[o * so + j * sj];
             xr = v.x;
             xi = conj ? -v.y : v.y;
+            if (rowscale) {
+                const float s = rowscale[o];
+                xr = s * xr;
+                xi = s * xi;
+            }
         }
         wt[wpack_index(2 * o, 2 * j, kap)] = xr;
         wt[wpack_index(2 * o, 2 * j + 1, kap)] = -xi;
@@ -501,13 +509,13 @@ __global__ __launch_bounds__(256) void weight_kband_ch_kernel(const float4* __re
 }
 
 int build_cweight_ch(const float2* src, size_t sg, long so, long sj, int conj, int O, int J, float* wt, size_t dg,
-                     int kap, int ncp, int nch, hipStream_t st) {
+                     int kap, int ncp, int nch, hipStream_t st, const float* rowscale, size_t rs) {
     AMP_REQUIRE(kap % GBK == 0 && ncp % 128 == 0 && nch >= 1 && nch <= WCH_MAX,
                 "build_cweight_ch: kap %d / ncp %d not tiled, or %d channels", kap, ncp, nch);
     const long total = (long)(ncp / 2) * (kap / 2);
     const int grid = (int)std::min<long>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(build_cweight_ch_kernel, dim3(grid, nch), dim3(256), 0, st, src, sg, so, sj, conj, O, J, wt, dg,
-                       kap, ncp);
+                       kap, ncp, rowscale, rs);
     AMP_LAUNCH_CHECK("build_cweight_ch");
     return AMP_OK;
 }
@@ -605,6 +613,52 @@ int gemm_store(const float* a, int lda, int rows, int ka, const float* wt, int k
     hipLaunchKernelGGL(gemm_store_kernel<128>, grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a, lda, rows, ka, wt,
                        kap, c, ldc, nc);
     AMP_LAUNCH_CHECK("gemm_store");
+    return AMP_OK;
+}
+
+// gemm_store_kernel with the row tile's channel (amp_trials.h channel_tile): the channel's operator,
+// its rows up to the channel's limit staged (the next channel's as zeros) and stored
+template <int BN, class AL = ALoadPlain>
+__global__ __launch_bounds__(AMP_WG) void gemm_store_ch_kernel(const float* __restrict__ a, int lda, int rows, int ka,
+                                                               const float* __restrict__ wt, size_t dg, int kap,
+                                                               float* __restrict__ c, int ldc, int nc, int per, int tpg) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const GemmTile tile = xcd_tile();
+    TrialChannels CH{};
+    CH.per = per; CH.tpg = tpg;
+    const ChannelTile ct = channel_tile(CH, tile.rb, rows);
+    const int row0 = ct.row0, col0 = tile.cb * BN;
+    gemm_tile<BN>(AL{a, lda, ct.lim, ka}, wt + (size_t)ct.g * dg, kap, row0, col0, lds);
+    using C = GemmCfg<BN>;
+    for (int e = threadIdx.x; e < GBM * BN; e += AMP_WG) {
+        const int rho = e / BN, cc = e % BN;
+        const int row = row0 + rho, col = col0 + cc;
+        if (row < ct.lim && col < nc) c[(size_t)row * ldc + col] = lds[rho * C::LDC + cc];
+    }
+}
+
+int gemm_store_ch(const float* a, int lda, int rows, int ka, const float* wt, size_t dg, int kap, int ncp, float* c,
+                  int ldc, int nc, int per, int tpg, int nch, hipStream_t st) {
+    static bool attr = false;
+    if (!attr) {
+        int rc = set_lds_attr<128>((const void*)gemm_store_ch_kernel<128>);
+        if (!rc) rc = set_lds_attr<128>((const void*)gemm_store_ch_kernel<128, ALoadPair>);
+        if (rc) return rc;
+        attr = true;
+    }
+    AMP_REQUIRE(lda % 2 == 0 && ka % 2 == 0 && ka >= 2, "gemm_store_ch: lda %d / ka %d must be even", lda, ka);
+    AMP_REQUIRE(per >= 1 && tpg == cdiv(per, GBM) && nch == cdiv(rows, per) && nch <= WCH_MAX,
+                "gemm_store_ch: %d rows at %d per channel, %d tiles per channel, %d channels", rows, per, tpg, nch);
+    dim3 grid(nch * tpg, ncp / 128);
+    // as gemm_store: the pair loader where rows are only 8-byte aligned (a channel's first row may be odd;
+    // lda is even, so every row stays 8-byte aligned, and 16-byte aligned where lda % 4 == 0)
+    if (lda % 4 != 0 || ka % 4 != 0)
+        hipLaunchKernelGGL((gemm_store_ch_kernel<128, ALoadPair>), grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a,
+                           lda, rows, ka, wt, dg, kap, c, ldc, nc, per, tpg);
+    else
+        hipLaunchKernelGGL(gemm_store_ch_kernel<128>, grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a, lda, rows, ka,
+                           wt, dg, kap, c, ldc, nc, per, tpg);
+    AMP_LAUNCH_CHECK("gemm_store_ch");
     return AMP_OK;
 }
 

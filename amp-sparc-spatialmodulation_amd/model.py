@@ -102,15 +102,18 @@ class Model(nn.Module):
         channel detected as independent trials in one launch sequence (forward_trials), in chunks
         of at most group_trials; every trial keeps its own scalars, shift and exit, so the sweep
         equals the per-epoch loop.  res = 1 degenerates to single forward calls.
-        trial_channels (> 0, with group_trials = n, BAMP / SCAMP; opt-in): one forward_trials call may
-        hold the trials of up to trial_channels whole `res` blocks, each with its own channel, and at
-        most n trials (forward_trials(..., per_channel=res): amp_bamp_trials_ch_run /
-        amp_scamp_trials_ch_run), so the reference's default res = 1 is a channel per trial.  The
+        trial_channels (> 0, with group_trials = n, VAMP / BAMP / SCAMP; opt-in): one forward_trials call
+        may hold the trials of up to trial_channels whole `res` blocks, each with its own channel, and at
+        most n trials (forward_trials(..., per_channel=res): amp_vamp_trials_ch_run /
+        amp_bamp_trials_ch_run / amp_scamp_trials_ch_run), so the reference's default res = 1 is a
+        channel per trial.  VAMP hands over each block's (U, s, Vh), its SVD taken per channel as in
+        the per-epoch loop (vamp_model.py:45-61: channel, SVD, message, noise).  The
         inputs are still drawn in the reference's order and the Losses yielded in epoch order; a
         block longer than n goes through the single-channel chunks above.  The packed operators of G
         channels cost G times one channel's bytes: the channels per call are capped so that the
-        library's workspace query stays under trials_ws_limit bytes (a setting; default 4 GiB).
-        'vamp' raises: its trial engine would need per-channel singular values in its scalar chain.
+        library's workspace query stays under trials_ws_limit bytes (a setting; default 4 GiB: VAMP's
+        three dense operators leave one channel per call at the published Nt = 1344 shape).
+        A 'vamp' detector object without a true `trials_per_channel` attribute raises.
         shard (with torch.distributed): 'epochs' (default) gives each rank whole epochs with its
         own random stream and merges the metrics once per SNR point; 'trials' (SURVEY §8(e)
         exact-compat, VAMP / BAMP / SCAMP) gives every rank the SAME epochs (one seed) and splits each batch's
@@ -174,9 +177,9 @@ class Model(nn.Module):
                 raise ValueError(f'trial_channels must be >= 0, got {trial_channels}')
             if not group_trials:
                 raise ValueError('trial_channels: set group_trials (the most trials per call) as well')
-            if detector not in ('bamp', 'scamp'):
-                raise ValueError('trial_channels: trial batches over several channels are built for the BAMP and '
-                                 'SCAMP detectors (VAMP would need per-channel singular values in its scalar chain)')
+            if detector not in ('bamp', 'scamp') and not getattr(self.amp, 'trials_per_channel', False):
+                raise ValueError('trial_channels: trial batches over several channels need a detector whose '
+                                 'forward_trials takes per_channel (BAMP, SCAMP, and VAMP with trials_per_channel)')
             self.channels_cap = int(trial_channels)
         if group_trials:
             if group_trials < 0:
@@ -283,18 +286,22 @@ class Model(nn.Module):
         return k
 
     def _detect_trials(self, SNR: float, chans: list, run: list, per_channel):
-        """One detection of the trials `run` ([(x, sym, idx, y)]): the plain forward for one trial,
-        the single-channel forward_trials for one channel, else the several-channel form."""
+        """One detection of the trials `run` ([(x, sym, idx, y)]) on the channels `chans` (VAMP: each
+        an (U, s, Vh)): the plain forward for one trial, the single-channel forward_trials for one
+        channel, else the several-channel form."""
         head = (self._W,) if self.detector == 'scamp' else ()
         if len(run) == 1:
             x, sym, idx, y = run[0]
-            ch = self._svd if self.detector == 'vamp' else head + (chans[0],)
+            ch = chans[0] if self.detector == 'vamp' else head + (chans[0],)
             yield self.amp(*ch, y, SNR, x, sym, idx)
             return
         cols = [[v[j] for v in run] for j in (3, 0, 1, 2)]        # ys, xs, symbols, indices
         if len(chans) == 1:
-            ch = self._svd if self.detector == 'vamp' else head + (chans[0],)
+            ch = chans[0] if self.detector == 'vamp' else head + (chans[0],)
             yield from self.amp.forward_trials(*ch, cols[0], SNR, *cols[1:])
+        elif self.detector == 'vamp':
+            Us, ss, Vhs = ([c[j] for c in chans] for j in range(3))
+            yield from self.amp.forward_trials(Us, ss, Vhs, cols[0], SNR, *cols[1:], per_channel=per_channel)
         else:
             yield from self.amp.forward_trials(*head, list(chans), cols[0], SNR, *cols[1:], per_channel=per_channel)
 
@@ -319,7 +326,7 @@ class Model(nn.Module):
                     yield from flush()
                 run.append(self._inputs(SNR, new))
                 if not chans:
-                    chans.append(self._A)
+                    chans.append(self._svd if self.detector == 'vamp' else self._A)
             yield from flush()
             return
         cap = self._blocks_per_call(res)
@@ -329,7 +336,7 @@ class Model(nn.Module):
                 yield from flush()
             run.append(self._inputs(SNR, new))
             if new or not chans:
-                chans.append(self._A)
+                chans.append(self._svd if self.detector == 'vamp' else self._A)
         yield from flush()
 
     def _per_epoch_channels(self) -> bool:

@@ -41,21 +41,57 @@ def _channel_stack(H, E: int, per_channel, what: str):
     [n, N] matrices or one [G, n, N] tensor, trial e using channel e // per_channel.  Returns
     (c64 [G, n, N] contiguous, per_channel, n, N); ValueError unless G == ceil(E / per_channel),
     raised before any tensor is touched."""
-    if per_channel is None or int(per_channel) < 1:
-        raise ValueError(f'forward_trials: {what} given as several channels needs per_channel >= 1 '
-                         f'(got {per_channel!r})')
-    R = int(per_channel)
-    mats = list(H) if isinstance(H, (list, tuple)) else None
-    G = len(mats) if mats is not None else (H.shape[0] if H.dim() == 3 else 1)
-    want = -(-E // R)
-    if G != want:
-        raise ValueError(f'forward_trials: {G} channels for {E} trials at per_channel = {R} '
-                         f'(trial e uses channel e // per_channel: expected {want})')
+    mats, G, R = _channel_count(H, E, per_channel, what, 3)
     one = mats[0] if mats is not None else H
     n, N = one.shape[-2], one.shape[-1]
     if mats is None:
         return _c64(H, (G, n, N)), R, n, N              # no copy of a contiguous c64 [G, n, N]
     return torch.stack([_c64(m, (n, N)) for m in mats]).contiguous(), R, n, N
+
+
+def _channel_count(H, E: int, per_channel, what: str, nd: int):
+    """_channel_stack's checks alone (no tensor is touched): `H` a list of G per-channel tensors or one
+    stacked tensor of `nd` dimensions.  Returns (the list or None, G, per_channel)."""
+    if per_channel is None or int(per_channel) < 1:
+        raise ValueError(f'forward_trials: {what} given as several channels needs per_channel >= 1 '
+                         f'(got {per_channel!r})')
+    R = int(per_channel)
+    mats = list(H) if isinstance(H, (list, tuple)) else None
+    G = len(mats) if mats is not None else (H.shape[0] if H.dim() == nd else 1)
+    want = -(-E // R)
+    if G != want:
+        raise ValueError(f'forward_trials: {G} channels for {E} trials at per_channel = {R} '
+                         f'(trial e uses channel e // per_channel: expected {want})')
+    return mats, G, R
+
+
+def _svd_channel_stack(U, s, Vh, E: int, per_channel):
+    """The channels of VAMP.forward_trials over several channels: each of U, s, Vh a list of G
+    per-channel factors or one stacked tensor ([G, n, k], [G, k], [G, k, N]).  Returns (c64 [G, n, k],
+    f32 [G, k], c64 [G, k, N], per_channel, n, k, N), contiguous (a contiguous stacked tensor of that
+    dtype is not copied); ValueError, raised before any tensor is touched, unless each holds
+    G == ceil(E / per_channel) channels and their shapes agree."""
+    (Us, G, R), (ss, _, _), (Vhs, _, _) = (_channel_count(U, E, per_channel, 'U', 3),
+                                          _channel_count(s, E, per_channel, 's', 2),
+                                          _channel_count(Vh, E, per_channel, 'Vh', 3))
+
+    def shapes(mats, t, nd):     # per channel (a stacked tensor: one shape for all)
+        return [tuple(m.shape) for m in mats] if mats is not None else [tuple(t.shape[1:] if t.dim() == nd else t.shape)]
+    shu, shs, shv = shapes(Us, U, 3), shapes(ss, s, 2), shapes(Vhs, Vh, 3)
+    if any(len(sh) < 2 for sh in shu + shv):
+        raise ValueError(f'forward_trials: U and Vh are matrices per channel (got shapes {shu[0]}, {shv[0]})')
+    n, k = shu[0][-2], shu[0][-1]
+    N = shv[0][-1]
+    numel = lambda sh: int(np.prod(sh))   # noqa: E731
+    if (any(sh != (n, k) for sh in shu) or any(sh != (k, N) for sh in shv) or any(numel(sh) != k for sh in shs)):
+        raise ValueError(f'forward_trials: the channels\' factors disagree in shape (U {sorted(set(shu))}, '
+                         f's {sorted(set(shs))}, Vh {sorted(set(shv))}: expected [n, k], [k], [k, N])')
+    f32 = lambda v: v.reshape(k).to(torch.float32).resolve_neg()   # noqa: E731
+    Uc = _c64(U, (G, n, k)) if Us is None else torch.stack([_c64(m, (n, k)) for m in Us]).contiguous()
+    Vhc = _c64(Vh, (G, k, N)) if Vhs is None else torch.stack([_c64(m, (k, N)) for m in Vhs]).contiguous()
+    sc = (s.reshape(G, k).to(torch.float32).resolve_neg().contiguous() if ss is None
+          else torch.stack([f32(v) for v in ss]).contiguous())
+    return Uc, sc, Vhc, R, n, k, N
 
 
 _FUSED_DECIDE = os.environ.get('AMP_FUSED_DECIDE', '1') != '0'
@@ -630,7 +666,18 @@ class VAMP(LazyResult, nn.Module):
         self.last_epochs = (r.view(E, B, N, 1), xm.view(E, B, N, 1), var.view(E, B, N, 1))
         return out
 
-    def forward_trials(self, U, s, Vh, ys, SNR: float, xs, symbols, indices) -> list:
+    trials_per_channel = True    # forward_trials takes per_channel (Model's trial_channels)
+
+    def trials_workspace_bytes(self, trials: int, per_channel: int) -> int:
+        """Workspace bytes of a forward_trials call of `trials` trials at `per_channel` per channel
+        (amp_vamp_trials_ch_workspace_bytes; 0: the call would be refused)."""
+        cfg = self.config
+        d = cfg.dims()
+        k = min(cfg.Nr * cfg.Lout, cfg.Nt * cfg.Lin)
+        return int(nat.lib().amp_vamp_trials_ch_workspace_bytes(C.byref(d), k, cfg.N_Layers, int(trials),
+                                                                int(per_channel)))
+
+    def forward_trials(self, U, s, Vh, ys, SNR: float, xs, symbols, indices, per_channel: int | None = None) -> list:
         """E independent single-trial detections that share ONE channel (U, s, Vh) and one SNR, in
         one launch sequence (amp_vamp_trials_run) — the epochs of one `res` block of the
         reference's drivers, which run batch = 1 (vamp_model.py:91, 98).  Each trial is the B = 1
@@ -640,23 +687,38 @@ class VAMP(LazyResult, nn.Module):
         order) that equal E sequential forward() calls; they resolve lazily, like forward_epochs'.
         ys / xs: sequences of the trials' y [1, n, 1] and x [1, N, 1], or stacked [E, ...] tensors;
         symbols / indices: sequences of their label arrays or stacked label tensors.
-        ValueError unless config.B == 1."""
+        ValueError unless config.B == 1.
+        Several channels (amp_vamp_trials_ch_run; vamp_model.py:45-61 redraws the channel every `res`
+        epochs): per_channel = R with each of U, s, Vh a list of G factors or one stacked [G, ...]
+        tensor; trial e then uses channel e // R (the last channel may hold fewer than R trials;
+        R = 1 is a channel per trial), and each trial still equals its own forward() with its own
+        (U, s, Vh).  ValueError unless each holds G == ceil(E / R) channels of agreeing shapes.
+        Without per_channel it is the one-channel call."""
         E = self._trials_check(ys, xs, symbols, indices)
         if self.engine == nat.ENGINE_PERSISTENT:
             raise ValueError('forward_trials runs on the launch engine (the persistent engine has no '
                              'independent-trial form)')
+        multi = per_channel is not None or isinstance(U, (list, tuple))
+        if multi:
+            Uc, sc, Vhc, R, n, k, N = _svd_channel_stack(U, s, Vh, E, per_channel)
         dev = ys[0].device
         self._ops.clear()
         with torch.cuda.device(dev):
             cfg = self.config
-            n, k, N = U.shape[-2], U.shape[-1], Vh.shape[-1]
-            Uc = _c64(U, (n, k))
-            sc = s.reshape(k).to(torch.float32).resolve_neg().contiguous()
-            Vhc = _c64(Vh, (k, N))
+            if multi:
+                Uc, sc, Vhc = Uc.to(dev), sc.to(dev), Vhc.to(dev)
+            else:
+                n, k, N = U.shape[-2], U.shape[-1], Vh.shape[-1]
+                Uc = _c64(U, (n, k))
+                sc = s.reshape(k).to(torch.float32).resolve_neg().contiguous()
+                Vhc = _c64(Vh, (k, N))
             y, x, sym, idx, res, host, dec = self._trials_inputs(ys, xs, symbols, indices, E, n, dev)
             d, cst = cfg.dims(), cfg.constellation()
             lib = nat.lib()
-            wsb = lib.amp_vamp_trials_workspace_bytes(C.byref(d), k, cfg.N_Layers, E)
+            if multi:
+                wsb = lib.amp_vamp_trials_ch_workspace_bytes(C.byref(d), k, cfg.N_Layers, E, R)
+            else:
+                wsb = lib.amp_vamp_trials_workspace_bytes(C.byref(d), k, cfg.N_Layers, E)
             if wsb == 0:
                 raise ValueError('amp_vamp_trials_workspace_bytes: invalid dimensions')
             ws = nat.WORKSPACE.get(dev, 'vamp_trials', wsb)
@@ -671,8 +733,12 @@ class VAMP(LazyResult, nn.Module):
             a.r, a.xmmse, a.var = nat.dptr(r), nat.dptr(xm), nat.dptr(var)
             a.status = nat.dptr(res)
             a.ws, a.ws_bytes = nat.dptr(ws), ws.numel()
-            nat.check(lib.amp_vamp_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
-                                              nat.stream_ptr(dev)), 'amp_vamp_trials_run')
+            if multi:
+                nat.check(lib.amp_vamp_trials_ch_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E, R,
+                                                     nat.stream_ptr(dev)), 'amp_vamp_trials_ch_run')
+            else:
+                nat.check(lib.amp_vamp_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
+                                                  nat.stream_ptr(dev)), 'amp_vamp_trials_run')
             out = self._trials_losses(res, host, E, dev)
             self._trials_keep = (y, x, sym, idx, Uc, sc, Vhc)   # alive until the kernels have read them
             self.last_trials = (r.view(E, 1, N, 1), xm.view(E, 1, N, 1), var.view(E, 1, N, 1))

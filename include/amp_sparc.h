@@ -598,6 +598,22 @@ int amp_bamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const 
 size_t amp_scamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel);
 int amp_scamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
                             const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream);
+/* The same for VAMP (vamp_model.py:45-61: the channel and its SVD are redrawn every `res` epochs).
+ * The factors of the G channels lie back to back: a->U c64 [G][n][k], a->s f32 [G][k], a->Vh c64
+ * [G][k][N].  Each channel's own singular values scale its packed s U^H (y~, vamp.py:22), enter its
+ * trials' LMMSE step (vamp.py:68) and their scalar chain (mean(scale), vamp.py:68-71), iteration 0's
+ * record included.  Everything else as amp_vamp_trials_run (launch-engine shapes: odd n, odd k, a
+ * partial last column tile; f32 GEMMs; dec may be NULL): every trial is bit for bit its own B = 1
+ * launch-engine forward with its own (U, s, Vh).  The workspace holds G copies of the three packed
+ * operators and of s2: with per_channel >= trials the query returns exactly
+ * amp_vamp_trials_workspace_bytes, otherwise that plus (G - 1) times one channel's operators and
+ * s2; 0 where the run would refuse.  AMP_E_ARG, before any pointer is read, for per_channel < 1,
+ * G > 65535 (a grid axis), d->B != 1, the persistent engine, a split-precision gemm and null
+ * pointers. */
+size_t amp_vamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t k, int32_t max_iter, int32_t trials,
+                                          int32_t per_channel);
+int amp_vamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
+                           const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream);
 
 /* ---- Element-wise shrinkage denoisers — replace Shrink (shrink.py:8-166).
  * r: [count] complex64 (is_complex != 0) or float32; cov: cov_vec [count] float32, or
