@@ -13,9 +13,11 @@
 // row with one partial per (tile, row); then tbamp_r, a grid over the trials: workgroup e reduces
 // trial e's partials, settles its exact float64 fix-up (fixup_sections, against the trial's own
 // max|xi|) and its allclose exit.  Every kernel returns at once when the stop counter has reached E.
-// amp_bamp_trials_ch_run: the same over G channels, trial e on channel e / per_channel: the channel
-// forms of the four GEMM kernels (tbamp_ka1_ch ... tbamp_kb2_ch) and the operators of all channels
-// packed in a number of launches that does not depend on G; tbamp_r as it is.
+// amp_bamp_trials_ch_run: the same over G channels, trial e on channel e / per_channel.  One kernel
+// family serves both entries: the four GEMM kernels are templates over the channel mapping
+// (amp_trials.h: OneChannel where the call has one channel, TrialChannels for several), one host
+// function runs either, and the operators of all channels are packed in a number of launches that
+// does not depend on G; tbamp_r is per trial.
 #include <algorithm>
 #include <mutex>
 
@@ -46,8 +48,8 @@ struct TBampWs {
     size_t bytes;
 };
 
-// G: channels whose packed operators and band ranges the workspace holds (amp_bamp_trials_ch_run;
-// one channel: the layout and bytes of amp_bamp_trials_run)
+// G: channels whose packed operators and band ranges the workspace holds (one channel keeps the dense
+// band ranges: the bytes amp_bamp_trials_workspace_bytes answers)
 static TBampWs tbamp_carve(const amp_dims* d, int E, void* base, int G = 1) {
     BampK P;
     bamp_geometry(d, E, P);
@@ -75,143 +77,81 @@ static TBampWs tbamp_carve(const amp_dims* d, int E, void* base, int G = 1) {
     return w;
 }
 
-// The entry guard of every GEMM kernel: false (workgroup-uniform) when every trial has stopped or
-// no row of this tile is live; s_stop then holds the tile's row flags for LiveRows.
-__device__ __forceinline__ bool tbamp_tile_live(const BampK& P, const BampTrials& R, int row0, int* s_stop) {
-    if (*R.nstop >= (unsigned)P.B) return false;
-    return tile_rows_live(R.iters, row0, P.B, s_stop);
-}
-
-// KC: the A chunk of the f32 tile, as amp_bamp.hip launches it (256 at the narrow column tile);
-// the chunking does not change the MFMA order: the same bits.
-// bamp_ka1.  AL: var's loader (ALoadPair where N % 4 == 2)
-template <class AL>
-__global__ __launch_bounds__(AMP_WG) void tbamp_ka1(BampK P, BampTrials R, int t) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ int s_stop[GBM];
-    const GemmTile tile = xcd_tile();
-    const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
-    if (!tbamp_tile_live(P, R, row0, s_stop)) return;
-    gemm_tile<128, AL, 256>(AL{bvar(P, t + 1), P.N, P.B, P.N}, P.Wabs2, P.kapA1, row0, col0, lds,
-                            bkb(P, 0, tile.cb), bke(P, 0, tile.cb));
-    bamp_store_v(P, LiveRows{s_stop}, lds, row0, col0);
-}
-
-// bamp_ka2
-__global__ __launch_bounds__(AMP_WG) void tbamp_ka2(BampK P, BampTrials R, int t) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ int s_stop[GBM];
-    const GemmTile tile = xcd_tile();
-    const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
-    if (!tbamp_tile_live(P, R, row0, s_stop)) return;
-    const int twoN = 2 * P.N;
-    gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.xm, twoN, P.B, twoN}, P.WH, P.kapA2, row0, col0, lds,
-                                    bkb(P, 1, tile.cb), bke(P, 1, tile.cb));
-    bamp_residual(P, LiveRows{s_stop}, lds, row0, col0);
-}
-
-// bamp_kb1
-__global__ __launch_bounds__(AMP_WG) void tbamp_kb1(BampK P, BampTrials R, int t) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ int s_stop[GBM];
-    const GemmTile tile = xcd_tile();
-    const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
-    if (!tbamp_tile_live(P, R, row0, s_stop)) return;
-    gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.invu, P.ild, P.B, P.ild}, P.Wabs2T, P.kapB1, row0, col0, lds,
-                                    bkb(P, 2, tile.cb), bke(P, 2, tile.cb));
-    bamp_store_cov(P, LiveRows{s_stop}, lds, row0, col0);
-}
-
-// bamp_kb2, the denoiser row by row: each live row's own partial, in the slot its B = 1 forward
-// stores it to, from scratch past the C tile (later rows still read the tile and the 1 / tau tile)
-template <int BN, int KK, int KC>
-__global__ __launch_bounds__(AMP_WG) void tbamp_kb2(BampK P, BampTrials R, int t) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ int s_stop[GBM];
-    using C = GemmCfg<BN, KC>;
-    const GemmTile tile = xcd_tile();
-    const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    if (!tbamp_tile_live(P, R, row0, s_stop)) return;
-    gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, P.sld, P.B, P.sld}, P.WHH, P.kapB2, row0, col0, lds,
-                                  bkb(P, 3, tile.cb), bke(P, 3, tile.cb));
-    const int nrows = min(GBM, P.B - row0), ncols = min(BN, 2 * P.N - col0);
-    const float* sit = bamp_xmap<BN, KC>(P, LiveRows{s_stop}, lds, row0, col0, nrows, ncols);
-    const int nct = P.ncpB2 / BN, slot = seq_part_slot(tile.cb, nct);
-    for (int rho = 0; rho < nrows; ++rho) {
-        if (s_stop[rho]) continue;   // workgroup-uniform
-        const BampDenoisePolicy pol = bamp_policy<BN, KC>(P, t, lds, sit, row0, col0, ncols, rho);
-        PartAcc pa;
-        denoise_sections<true, KK>(pol, pol.spr, P.M, P.c, pa);
-        part_block_store(pa, P.parts + (size_t)(row0 + rho) * nct + slot, lds + C::CTILE_FLOATS);
-    }
-}
-
-// ---- the channel forms of the four GEMM kernels (amp_bamp_trials_ch_run): row tile rb belongs to
-// channel rb / tpg (amp_trials.h channel_tile).  The kernel takes the channel's view of the
-// parameter block at its entry (operator w and its band ranges), stages and guards its rows up to
-// the channel's limit, and runs the same gemm_tile call and epilogue: a row has the bits of its own
-// B = 1 forward with that channel, wherever in a tile it lies (a first row that is no multiple of
-// 32, or odd, changes no alignment: every row stride is even, lda of ALoadPair's 8-byte loads
-// included).  The stop counter is still compared with E (P.B); tbamp_r runs as it is. ----
-
-// false (workgroup-uniform) when every trial has stopped or no row of the tile is live; else P holds
-// channel ct.g's operator w and band ranges
-__device__ __forceinline__ bool tbamp_ch_enter(BampK& P, const BampTrials& R, const TrialChannels& CH,
-                                               const ChannelTile& ct, int w, const float*& wt, int* s_stop) {
+// The entry of every GEMM kernel.  false (workgroup-uniform) when every trial has stopped or no row
+// of the tile is live (rows up to the channel's limit; s_stop then holds the tile's row flags for
+// LiveRows); else P holds channel ct.g's operator w and band ranges.  The stop counter is compared
+// with E (P.B) whatever the channels.
+template <class CH>
+__device__ __forceinline__ bool tbamp_enter(BampK& P, const BampTrials& R, const CH& ch, const ChannelTile& ct, int w,
+                                            const float*& wt, int* s_stop) {
     if (*R.nstop >= (unsigned)P.B) return false;
     if (!tile_rows_live(R.iters, ct.row0, ct.lim, s_stop)) return false;
-    wt += (size_t)ct.g * CH.wstride[w];
-    if (P.band[w]) P.band[w] += (size_t)ct.g * CH.bstride[w];
+    wt += ch.woff(ct.g, w);
+    if (P.band[w]) P.band[w] += ch.boff(ct.g, w);
     return true;
 }
 
-template <class AL>
-__global__ __launch_bounds__(AMP_WG) void tbamp_ka1_ch(BampK P, BampTrials R, TrialChannels CH, int t) {
+// The four GEMM kernels, each written once over the channel mapping CH (amp_trials.h): row tile rb
+// is channel ct.g's, its rows staged and guarded up to ct.lim, then the launch engine's gemm_tile
+// call and epilogue: a row has the bits of its own B = 1 forward with that channel, wherever in a
+// tile it lies (a first row that is no multiple of 32, or odd, changes no alignment: every row
+// stride is even, lda of ALoadPair's 8-byte loads included).
+// KC: the A chunk of the f32 tile, as amp_bamp.hip launches it (256 at the narrow column tile);
+// the chunking does not change the MFMA order: the same bits.
+// bamp_ka1.  AL: var's loader (ALoadPair where N % 4 == 2)
+template <class AL, class CH>
+__global__ __launch_bounds__(AMP_WG) void tbamp_ka1(BampK P, BampTrials R, CH ch, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_stop[GBM];
     const GemmTile tile = xcd_tile();
-    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const ChannelTile ct = ch.tile(tile.rb, P.B);
     const int row0 = ct.row0, col0 = tile.cb * 128;
-    if (!tbamp_ch_enter(P, R, CH, ct, 0, P.Wabs2, s_stop)) return;
+    if (!tbamp_enter(P, R, ch, ct, 0, P.Wabs2, s_stop)) return;
     gemm_tile<128, AL, 256>(AL{bvar(P, t + 1), P.N, ct.lim, P.N}, P.Wabs2, P.kapA1, row0, col0, lds,
                             bkb(P, 0, tile.cb), bke(P, 0, tile.cb));
     bamp_store_v(P, LiveRows{s_stop}, lds, row0, col0);
 }
 
-__global__ __launch_bounds__(AMP_WG) void tbamp_ka2_ch(BampK P, BampTrials R, TrialChannels CH, int t) {
+// bamp_ka2
+template <class CH>
+__global__ __launch_bounds__(AMP_WG) void tbamp_ka2(BampK P, BampTrials R, CH ch, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_stop[GBM];
     const GemmTile tile = xcd_tile();
-    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const ChannelTile ct = ch.tile(tile.rb, P.B);
     const int row0 = ct.row0, col0 = tile.cb * 128;
-    if (!tbamp_ch_enter(P, R, CH, ct, 1, P.WH, s_stop)) return;
+    if (!tbamp_enter(P, R, ch, ct, 1, P.WH, s_stop)) return;
     const int twoN = 2 * P.N;
     gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.xm, twoN, ct.lim, twoN}, P.WH, P.kapA2, row0, col0, lds,
                                     bkb(P, 1, tile.cb), bke(P, 1, tile.cb));
     bamp_residual(P, LiveRows{s_stop}, lds, row0, col0);
 }
 
-__global__ __launch_bounds__(AMP_WG) void tbamp_kb1_ch(BampK P, BampTrials R, TrialChannels CH, int t) {
+// bamp_kb1
+template <class CH>
+__global__ __launch_bounds__(AMP_WG) void tbamp_kb1(BampK P, BampTrials R, CH ch, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_stop[GBM];
     const GemmTile tile = xcd_tile();
-    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const ChannelTile ct = ch.tile(tile.rb, P.B);
     const int row0 = ct.row0, col0 = tile.cb * 128;
-    if (!tbamp_ch_enter(P, R, CH, ct, 2, P.Wabs2T, s_stop)) return;
+    if (!tbamp_enter(P, R, ch, ct, 2, P.Wabs2T, s_stop)) return;
     gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.invu, P.ild, ct.lim, P.ild}, P.Wabs2T, P.kapB1, row0, col0, lds,
                                     bkb(P, 2, tile.cb), bke(P, 2, tile.cb));
     bamp_store_cov(P, LiveRows{s_stop}, lds, row0, col0);
 }
 
-template <int BN, int KK, int KC>
-__global__ __launch_bounds__(AMP_WG) void tbamp_kb2_ch(BampK P, BampTrials R, TrialChannels CH, int t) {
+// bamp_kb2, the denoiser row by row: each live row's own partial, in the slot its B = 1 forward
+// stores it to, from scratch past the C tile (later rows still read the tile and the 1 / tau tile)
+template <int BN, int KK, int KC, class CH>
+__global__ __launch_bounds__(AMP_WG) void tbamp_kb2(BampK P, BampTrials R, CH ch, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_stop[GBM];
     using C = GemmCfg<BN, KC>;
     const GemmTile tile = xcd_tile();
-    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const ChannelTile ct = ch.tile(tile.rb, P.B);
     const int row0 = ct.row0, col0 = tile.cb * BN;
-    if (!tbamp_ch_enter(P, R, CH, ct, 3, P.WHH, s_stop)) return;
+    if (!tbamp_enter(P, R, ch, ct, 3, P.WHH, s_stop)) return;
     gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, P.sld, ct.lim, P.sld}, P.WHH, P.kapB2, row0, col0, lds,
                                   bkb(P, 3, tile.cb), bke(P, 3, tile.cb));
     const int nrows = min(GBM, ct.lim - row0), ncols = min(BN, 2 * P.N - col0);
@@ -292,40 +232,32 @@ static int tbamp_attrs() {
     std::call_once(g_tbamp_once, [] {
         for (int K : {1, 2, 4, 8, 16, 64})
             dispatch_K(K, [](auto kk) {
-                if (!g_tbamp_rc) g_tbamp_rc = set_lds_attr<256>((const void*)tbamp_kb2<256, decltype(kk)::value, GKC>);
+                constexpr int KK = decltype(kk)::value;
+                if (!g_tbamp_rc) g_tbamp_rc = set_lds_attr<256>((const void*)tbamp_kb2<256, KK, GKC, OneChannel>);
+                if (!g_tbamp_rc) g_tbamp_rc = set_lds_attr<256>((const void*)tbamp_kb2<256, KK, GKC, TrialChannels>);
             });
     });
     return g_tbamp_rc;
 }
 
-template <int KK>
-static void tbamp_launch_kb2(const BampK& P, const BampTrials& R, int gr, int t, hipStream_t st) {
+template <int KK, class CH>
+static void tbamp_launch_kb2(const BampK& P, const BampTrials& R, const CH& ch, int gr, int t, hipStream_t st) {
     if (P.bn == 128)
-        hipLaunchKernelGGL((tbamp_kb2<128, KK, 256>), dim3(gr, P.ncpB2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, t);
+        hipLaunchKernelGGL((tbamp_kb2<128, KK, 256, CH>), dim3(gr, P.ncpB2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
     else
-        hipLaunchKernelGGL((tbamp_kb2<256, KK, GKC>), dim3(gr, P.ncpB2 / 256), dim3(AMP_WG), TB_LDS_W, st, P, R, t);
+        hipLaunchKernelGGL((tbamp_kb2<256, KK, GKC, CH>), dim3(gr, P.ncpB2 / 256), dim3(AMP_WG), TB_LDS_W, st, P, R, ch, t);
 }
 
-static std::once_flag g_tbamp_ch_once;
-static int g_tbamp_ch_rc = 0;
-static int tbamp_ch_attrs() {
-    std::call_once(g_tbamp_ch_once, [] {
-        for (int K : {1, 2, 4, 8, 16, 64})
-            dispatch_K(K, [](auto kk) {
-                if (!g_tbamp_ch_rc)
-                    g_tbamp_ch_rc = set_lds_attr<256>((const void*)tbamp_kb2_ch<256, decltype(kk)::value, GKC>);
-            });
-    });
-    return g_tbamp_ch_rc;
-}
-
-template <int KK>
-static void tbamp_launch_kb2_ch(const BampK& P, const BampTrials& R, const TrialChannels& CH, int gr, int t,
-                                hipStream_t st) {
-    if (P.bn == 128)
-        hipLaunchKernelGGL((tbamp_kb2_ch<128, KK, 256>), dim3(gr, P.ncpB2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, CH, t);
+// iteration t's four GEMM launches over gr row tiles
+template <class CH>
+static void tbamp_launch_gemms(const BampK& P, const BampTrials& R, const CH& ch, int gr, int t, hipStream_t st) {
+    if (P.N % 4 != 0)
+        hipLaunchKernelGGL((tbamp_ka1<ALoadPair, CH>), dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
     else
-        hipLaunchKernelGGL((tbamp_kb2_ch<256, KK, GKC>), dim3(gr, P.ncpB2 / 256), dim3(AMP_WG), TB_LDS_W, st, P, R, CH, t);
+        hipLaunchKernelGGL((tbamp_ka1<ALoadPlain, CH>), dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
+    hipLaunchKernelGGL(tbamp_ka2<CH>, dim3(gr, P.ncpA2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
+    hipLaunchKernelGGL(tbamp_kb1<CH>, dim3(gr, P.ncpB1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
+    dispatch_K(P.c.K, [&](auto kk) { tbamp_launch_kb2<decltype(kk)::value>(P, R, ch, gr, t, st); });
 }
 
 // The operators of G channels (H: c64 [G][n][N]) and their band ranges, each channel's own, in a
@@ -348,108 +280,31 @@ static int tbamp_pack_ch(const BampK& P, const TrialChannels& CH, const float2* 
     return AMP_OK;
 }
 
-}  // namespace amp
-
-using namespace amp;
-
-extern "C" {
-
-size_t amp_bamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials) {
-    if (!d || max_iter <= 0 || trials <= 0 || d->B != 1) return 0;
-    return tbamp_carve(d, trials, nullptr).bytes;
-}
-
-int amp_bamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
-                        const amp_trials_decide_args* dec, int32_t trials, void* stream) {
+// Both entries.  fn: the entry that was called (amp_bamp_trials_run passes per_channel = trials: one
+// channel); a->H holds the G = ceil(trials / per_channel) channels in order.
+static int tbamp_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
+                     const amp_trials_decide_args* dec, int trials, int per_channel, const char* fn, hipStream_t st) {
     int rc = check_dims(d, c, true, true);   // any n, any even N, a partial last column tile (amp_bamp_run)
     if (rc) return rc;
-    AMP_REQUIRE(d->B == 1, "amp_bamp_trials_run: dims describe ONE trial (B = %d, must be 1)", d->B);
-    AMP_REQUIRE(trials >= 1, "amp_bamp_trials_run: trials = %d", trials);
-    AMP_REQUIRE(bamp_index_ok(d, trials), "amp_bamp_trials_run: %d trials of max(2N, 2n) = %d columns need more "
-                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
-    AMP_REQUIRE(a && a->H && a->y && a->xmap && a->xmmse && a->var && a->status && a->ws,
-                "amp_bamp_trials_run: null pointer argument");
-    AMP_REQUIRE(a->max_iter > 0, "amp_bamp_trials_run: max_iter must be positive");
-    AMP_REQUIRE(a->denoiser == 0, "amp_bamp_trials_run: the element-wise denoiser ('random' mode) has no "
-                "independent-trial form");
-    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "amp_bamp_trials_run: f32 GEMMs only (gemm %d)",
-                a->gemm);
-    const int E = trials;
-    const TBampWs w = tbamp_carve(d, E, a->ws);
-    AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_bamp_trials_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
-    TrialsDecide td{};
-    if (dec && (rc = trials_decide_args(d, dec, a->xmap, a->xmmse, td))) return rc;
-    if ((rc = tbamp_attrs())) return rc;
-    BampK P{};             // f32 tiles, the block denoiser (h2 = x3 = elementwise = 0)
-    bamp_geometry(d, E, P);
-    P.max_iter = a->max_iter;
-    P.sigma2 = (float)a->noise_var;
-    P.Wabs2 = w.Wabs2; P.WH = w.WH; P.Wabs2T = w.Wabs2T; P.WHH = w.WHH;
-    P.y = (const float*)a->y; P.v = w.v; P.z = w.z; P.invu = w.invu; P.s = w.s; P.cov = w.cov;
-    P.xmap = (float*)a->xmap; P.xm = (float*)a->xmmse; P.var0 = (float*)a->var; P.var1 = w.var1;
-    P.secmax = w.secmax; P.secabs = w.secabs; P.parts = w.parts;
-    P.status = (amp_status*)a->status;
-    const bool band = d->Lin > 1 || d->Lout > 1;   // block-banded H (channel.py:75-95)
-    for (int i = 0; i < 4; ++i) P.band[i] = band ? w.band[i] : nullptr;
-    P.c = to_const(c);
-    const BampTrials R{w.iters, w.nstop};
-    const Const64 c64 = to_const64(c);
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = bamp_pack_f32(P, (const float2*)a->H, st))) return rc;   // the operators, packed once per call
-    const size_t tot = std::max((size_t)E * P.N, (size_t)E * P.n);
-    hipLaunchKernelGGL(tbamp_init_kernel, dim3((int)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, P, R);
-    AMP_LAUNCH_CHECK("tbamp_init");
-    const int gr = cdiv(E, GBM);
-    for (int t = 0; t < P.max_iter; ++t) {
-        if (P.N % 4 != 0)
-            hipLaunchKernelGGL(tbamp_ka1<ALoadPair>, dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, t);
-        else
-            hipLaunchKernelGGL(tbamp_ka1<ALoadPlain>, dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, t);
-        hipLaunchKernelGGL(tbamp_ka2, dim3(gr, P.ncpA2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, t);
-        hipLaunchKernelGGL(tbamp_kb1, dim3(gr, P.ncpB1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, t);
-        dispatch_K(P.c.K, [&](auto kk) { tbamp_launch_kb2<decltype(kk)::value>(P, R, gr, t, st); });
-        hipLaunchKernelGGL(tbamp_r, dim3(E), dim3(TBRWG), 0, st, P, R, c64, t);
-        AMP_LAUNCH_CHECK("tbamp iteration");
-    }
-    hipLaunchKernelGGL(tbamp_output_kernel, dim3(E), dim3(256), 0, st, P);
-    AMP_LAUNCH_CHECK("tbamp_output");
-    return dec ? trials_decide_launch(d, c, td, E, w.dec, st) : AMP_OK;
-}
-
-size_t amp_bamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel) {
-    if (!d || max_iter <= 0 || trials <= 0 || per_channel < 1 || d->B != 1) return 0;
-    if (d->N <= 0 || d->n <= 0 || d->M <= 0 || d->N % 2 != 0 || !bamp_index_ok(d, trials)) return 0;
-    int per = per_channel;
-    const int G = trial_channels(trials, per);
-    if (G > WCH_MAX) return 0;
-    return tbamp_carve(d, trials, nullptr, G).bytes;
-}
-
-int amp_bamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
-                           const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
-    int rc = check_dims(d, c, true, true);   // any n, any even N, a partial last column tile (amp_bamp_run)
-    if (rc) return rc;
-    AMP_REQUIRE(d->B == 1, "amp_bamp_trials_ch_run: dims describe ONE trial (B = %d, must be 1)", d->B);
-    AMP_REQUIRE(trials >= 1, "amp_bamp_trials_ch_run: trials = %d", trials);
-    AMP_REQUIRE(per_channel >= 1, "amp_bamp_trials_ch_run: per_channel = %d", per_channel);
-    AMP_REQUIRE(bamp_index_ok(d, trials), "amp_bamp_trials_ch_run: %d trials of max(2N, 2n) = %d columns need more "
-                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
-    AMP_REQUIRE(a && a->H && a->y && a->xmap && a->xmmse && a->var && a->status && a->ws,
-                "amp_bamp_trials_ch_run: null pointer argument");
-    AMP_REQUIRE(a->max_iter > 0, "amp_bamp_trials_ch_run: max_iter must be positive");
-    AMP_REQUIRE(a->denoiser == 0, "amp_bamp_trials_ch_run: the element-wise denoiser ('random' mode) has no "
-                "independent-trial form");
-    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "amp_bamp_trials_ch_run: f32 GEMMs only (gemm %d)",
-                a->gemm);
+    AMP_REQUIRE(d->B == 1, "%s: dims describe ONE trial (B = %d, must be 1)", fn, d->B);
+    AMP_REQUIRE(trials >= 1, "%s: trials = %d", fn, trials);
+    AMP_REQUIRE(per_channel >= 1, "%s: per_channel = %d", fn, per_channel);
+    AMP_REQUIRE(bamp_index_ok(d, trials), "%s: %d trials of max(2N, 2n) = %d columns need more than 32-bit offsets "
+                "(or more than 65535 column tiles)", fn, trials, 2 * std::max(d->N, d->n));
+    AMP_REQUIRE(a && a->H && a->y && a->xmap && a->xmmse && a->var && a->status && a->ws, "%s: null pointer argument",
+                fn);
+    AMP_REQUIRE(a->max_iter > 0, "%s: max_iter must be positive", fn);
+    AMP_REQUIRE(a->denoiser == 0, "%s: the element-wise denoiser ('random' mode) has no independent-trial form", fn);
+    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "%s: f32 GEMMs only (gemm %d)", fn, a->gemm);
     const int E = trials;
     int per = per_channel;
     const int G = trial_channels(E, per);
-    AMP_REQUIRE(G <= WCH_MAX, "amp_bamp_trials_ch_run: %d channels (at most %d per call: a grid axis)", G, WCH_MAX);
+    AMP_REQUIRE(G <= WCH_MAX, "%s: %d channels (at most %d per call: a grid axis)", fn, G, WCH_MAX);
     const TBampWs w = tbamp_carve(d, E, a->ws, G);
-    AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_bamp_trials_ch_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
+    AMP_REQUIRE(a->ws_bytes >= w.bytes, "%s: workspace %zu < %zu bytes", fn, a->ws_bytes, w.bytes);
     TrialsDecide td{};
     if (dec && (rc = trials_decide_args(d, dec, a->xmap, a->xmmse, td))) return rc;
-    if ((rc = tbamp_ch_attrs())) return rc;
+    if ((rc = tbamp_attrs())) return rc;
     BampK P{};             // f32 tiles, the block denoiser (h2 = x3 = elementwise = 0)
     bamp_geometry(d, E, P);
     P.max_iter = a->max_iter;
@@ -472,26 +327,52 @@ int amp_bamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const 
     }
     const BampTrials R{w.iters, w.nstop};
     const Const64 c64 = to_const64(c);
-    hipStream_t st = (hipStream_t)stream;
     if ((rc = tbamp_pack_ch(P, CH, (const float2*)a->H, G, st))) return rc;   // every channel's operators, once per call
     const size_t tot = std::max((size_t)E * P.N, (size_t)E * P.n);
     hipLaunchKernelGGL(tbamp_init_kernel, dim3((int)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, P, R);
     AMP_LAUNCH_CHECK("tbamp_init");
-    const int gr = G * CH.tpg;                     // <= E row tiles
+    const int gr = G * CH.tpg;                     // <= E row tiles; one channel: cdiv(E, 32)
     for (int t = 0; t < P.max_iter; ++t) {
-        if (P.N % 4 != 0)
-            hipLaunchKernelGGL(tbamp_ka1_ch<ALoadPair>, dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, CH, t);
+        if (G == 1)
+            tbamp_launch_gemms(P, R, OneChannel{}, gr, t, st);
         else
-            hipLaunchKernelGGL(tbamp_ka1_ch<ALoadPlain>, dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, CH, t);
-        hipLaunchKernelGGL(tbamp_ka2_ch, dim3(gr, P.ncpA2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, CH, t);
-        hipLaunchKernelGGL(tbamp_kb1_ch, dim3(gr, P.ncpB1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, CH, t);
-        dispatch_K(P.c.K, [&](auto kk) { tbamp_launch_kb2_ch<decltype(kk)::value>(P, R, CH, gr, t, st); });
+            tbamp_launch_gemms(P, R, CH, gr, t, st);
         hipLaunchKernelGGL(tbamp_r, dim3(E), dim3(TBRWG), 0, st, P, R, c64, t);
-        AMP_LAUNCH_CHECK("tbamp_ch iteration");
+        AMP_LAUNCH_CHECK("tbamp iteration");
     }
     hipLaunchKernelGGL(tbamp_output_kernel, dim3(E), dim3(256), 0, st, P);
     AMP_LAUNCH_CHECK("tbamp_output");
     return dec ? trials_decide_launch(d, c, td, E, w.dec, st) : AMP_OK;
+}
+
+}  // namespace amp
+
+using namespace amp;
+
+extern "C" {
+
+size_t amp_bamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials) {
+    if (!d || max_iter <= 0 || trials <= 0 || d->B != 1) return 0;
+    return tbamp_carve(d, trials, nullptr).bytes;
+}
+
+int amp_bamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
+                        const amp_trials_decide_args* dec, int32_t trials, void* stream) {
+    return tbamp_run(d, c, a, dec, trials, trials, "amp_bamp_trials_run", (hipStream_t)stream);
+}
+
+size_t amp_bamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel) {
+    if (!d || max_iter <= 0 || trials <= 0 || per_channel < 1 || d->B != 1) return 0;
+    if (d->N <= 0 || d->n <= 0 || d->M <= 0 || d->N % 2 != 0 || !bamp_index_ok(d, trials)) return 0;
+    int per = per_channel;
+    const int G = trial_channels(trials, per);
+    if (G > WCH_MAX) return 0;
+    return tbamp_carve(d, trials, nullptr, G).bytes;
+}
+
+int amp_bamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
+                           const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
+    return tbamp_run(d, c, a, dec, trials, per_channel, "amp_bamp_trials_ch_run", (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -289,13 +289,13 @@ int build_abs2_weight(const float2* src, long so, long sj, int O, int J, float* 
 // the tile is all zero).  One pass over the weight (amp_weights.hip).
 int weight_kband(const float* wp, int kap, int ncp, int BN, int* band, hipStream_t st);
 int h2_kband(const void* wq, int PL, int G, int tpt, int ntiles, int n16, int* band, hipStream_t st);
-// build_cweight (WPACK32, no row scale), build_abs2_weight and weight_kband for `nch` channels in one
-// launch each (three for the band ranges), the channel on a grid axis: channel g's source at
-// src + g * sg (float2 elements), its packed operator at wt + g * dg (floats), its band ranges at
-// band + g * bstride (ints; bstride even, >= 2 ncp / BN).  A channel's operator and ranges have the
-// bits of the single-channel calls on that channel alone.  rowscale (build_cweight_ch; null: none):
-// channel g's row scale at rowscale + g * rs floats, multiplied as build_cweight's (VAMP's
-// Wt0 = s * U^H with each channel's own singular values, amp_vamp_trials_ch_run).
+// build_cweight (WPACK32), build_abs2_weight and weight_kband for `nch` channels in one launch each
+// (three for the band ranges), the channel on a grid axis of the same kernels (the single-channel
+// functions are the nch = 1 case): channel g's source at src + g * sg (float2 elements), its packed
+// operator at wt + g * dg (floats), its band ranges at band + g * bstride (ints; bstride even,
+// >= 2 ncp / BN).  rowscale (build_cweight_ch; null: none): channel g's row scale at
+// rowscale + g * rs floats, multiplied as build_cweight's (VAMP's Wt0 = s * U^H with each channel's
+// own singular values, the trial engine).
 constexpr int WCH_MAX = 65535;   // channels per call: a grid axis
 int build_cweight_ch(const float2* src, size_t sg, long so, long sj, int conj, int O, int J, float* wt, size_t dg,
                      int kap, int ncp, int nch, hipStream_t st, const float* rowscale = nullptr, size_t rs = 0);
@@ -313,9 +313,9 @@ template <int BN>
 int set_lds_attr(const void* fn);
 int gemm_store(const float* a, int lda, int rows, int ka, const float* wt, int kap, int ncp, float* c, int ldc,
                int nc, hipStream_t st);
-// gemm_store over several channels (amp_trials.h channel_tile: row r uses channel r / per, tpg row
+// gemm_store over several channels (amp_trials.h TrialChannels: row r uses channel r / per, tpg row
 // tiles per channel, nch channels): row tile rb multiplies with the operator at wt + (rb / tpg) * dg
-// floats and stores its channel's rows only.  A row has the bits gemm_store gives it.
+// floats and stores its channel's rows only.  gemm_store is the call with one channel of all rows.
 int gemm_store_ch(const float* a, int lda, int rows, int ka, const float* wt, size_t dg, int kap, int ncp, float* c,
                   int ldc, int nc, int per, int tpg, int nch, hipStream_t st);
 

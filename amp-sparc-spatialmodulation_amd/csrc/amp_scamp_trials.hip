@@ -15,9 +15,11 @@
 // settles its exit or leaves a pending exact float64 fix-up in the trial's record, which
 // tscamp_fix_sec and tscamp_fix_psi_fin (also grids over the trials) carry out against the trial's
 // own max|xi|.  Every kernel returns at once when the stop counter has reached E.
-// amp_scamp_trials_ch_run: the same over G channels, trial e on channel e / per_channel: the channel
-// forms of the two GEMM kernels (tscamp_ka_ch, tscamp_kb_ch) and the operators of all channels
-// packed in a number of launches that does not depend on G; every other kernel as it is.
+// amp_scamp_trials_ch_run: the same over G channels, trial e on channel e / per_channel.  One kernel
+// family serves both entries: the two GEMM kernels are templates over the channel mapping
+// (amp_trials.h: OneChannel where the call has one channel, TrialChannels for several), one host
+// function runs either, and the operators of all channels are packed in a number of launches that
+// does not depend on G; every other kernel is per trial.
 #include <algorithm>
 #include <mutex>
 
@@ -44,8 +46,8 @@ struct TScampWs {
     size_t bytes;
 };
 
-// G: channels whose packed operators and band ranges the workspace holds (amp_scamp_trials_ch_run;
-// one channel: the layout and bytes of amp_scamp_trials_run)
+// G: channels whose packed operators and band ranges the workspace holds (one channel keeps the dense
+// band ranges: the bytes amp_scamp_trials_workspace_bytes answers)
 static TScampWs tscamp_carve(const amp_dims* d, int E, void* base, int G = 1) {
     ScampK P;
     scamp_geometry(d, E, P);
@@ -72,92 +74,52 @@ static TScampWs tscamp_carve(const amp_dims* d, int E, void* base, int G = 1) {
     return w;
 }
 
-// The entry guard of every GEMM kernel: false (workgroup-uniform) when every trial has stopped or
-// no row of this tile is live; s_stop then holds the tile's row flags for LiveRows.
-__device__ __forceinline__ bool tscamp_tile_live(const ScampK& P, const ScampTrials& R, int row0, int* s_stop) {
+// The entry of both GEMM kernels.  false (workgroup-uniform) when every trial has stopped or no row
+// of the tile is live (rows up to the channel's limit; s_stop then holds the tile's row flags for
+// LiveRows); else operator w (0: A, 1: A^H) and its band ranges are channel ct.g's.  The stop
+// counter is compared with E (P.B) whatever the channels.
+template <class CH>
+__device__ __forceinline__ bool tscamp_enter(const ScampK& P, const ScampTrials& R, const CH& ch, const ChannelTile& ct,
+                                             int w, const float*& wt, const int*& band, int* s_stop) {
     if (*R.nstop >= (unsigned)P.B) return false;
-    return tile_rows_live(P.iters, row0, P.B, s_stop);
+    if (!tile_rows_live(P.iters, ct.row0, ct.lim, s_stop)) return false;
+    wt += ch.woff(ct.g, w);
+    if (band) band += ch.boff(ct.g, w);
+    return true;
 }
 
+// The two GEMM kernels, each written once over the channel mapping CH (amp_trials.h): row tile rb is
+// channel ct.g's, its rows staged and guarded up to ct.lim, then the launch engine's gemm_tile call
+// and epilogue: a row has the bits of its own B = 1 forward with that channel, wherever in a tile it
+// lies.
 // scamp_ka, every row on its own psi and phi.  KC = 256: the A chunk amp_scamp.hip launches for a
 // block-banded A; the chunking does not change the MFMA order: the same bits.
-__global__ __launch_bounds__(AMP_WG) void tscamp_ka(ScampK P, ScampTrials R, int t) {
+template <class CH>
+__global__ __launch_bounds__(AMP_WG) void tscamp_ka(ScampK P, ScampTrials R, CH ch, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_stop[GBM];
     const GemmTile tile = xcd_tile();
-    const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
-    if (!tscamp_tile_live(P, R, row0, s_stop)) return;
-    const int twoN = 2 * P.N;
-    const int kb = P.bandA ? P.bandA[2 * tile.cb] : 0, ke = P.bandA ? P.bandA[2 * tile.cb + 1] : -1;
-    gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.xm, twoN, P.B, twoN}, P.WA, P.kapA, row0, col0, lds, kb, ke);
-    scamp_residual<256>(P, LiveRows{s_stop}, t, lds, row0, col0);
-}
-
-// scamp_kb, the denoiser and the in-tile psi row by row: each live row's own partial, in the slot
-// its B = 1 forward stores it to, from scratch past the C tile (LiveRows::PSCR: later rows still
-// read the tile and the tau tile)
-template <int BN, int KK, int KC>
-__global__ __launch_bounds__(AMP_WG) void tscamp_kb(ScampK P, ScampTrials R, int t) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ int s_stop[GBM];
-    using C = GemmCfg<BN, KC>;
-    const GemmTile tile = xcd_tile();
-    const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    if (!tscamp_tile_live(P, R, row0, s_stop)) return;
-    const int sld = scamp_sld(P.n);
-    const int kb = P.bandB ? P.bandB[2 * tile.cb] : 0, ke = P.bandB ? P.bandB[2 * tile.cb + 1] : -1;
-    gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, sld, P.B, sld}, P.WAH, P.kapB, row0, col0, lds, kb, ke);
-    const int nrows = min(GBM, P.B - row0), ncols = min(BN, 2 * P.N - col0);
-    const ScampTileBlocks tb = scamp_tile_blocks(P, col0, ncols);
-    const float* tau_t = scamp_xmap<BN, KC>(P, LiveRows{s_stop}, t, lds, row0, col0, nrows, ncols, tb);
-    const int nct = P.ncpB / BN, slot = seq_part_slot(tile.cb, nct);
-    for (int rho = 0; rho < nrows; ++rho) {
-        if (s_stop[rho]) continue;   // workgroup-uniform
-        const ScampDenoisePolicy pol = scamp_policy<BN, KC>(P, lds, tau_t, row0, col0, ncols, tb, rho);
-        PartAcc pa;
-        denoise_sections<false, KK>(pol, pol.spr, P.M, P.c, pa);
-        __syncthreads();
-        if (!P.psi_split && (int)threadIdx.x < tb.nlc)
-            pa.notclose += scamp_psi_in_tile(P, t, row0 + rho, tb.lc0 + threadIdx.x);
-        part_block_store(pa, P.parts + (size_t)(row0 + rho) * nct + slot, lds + C::CTILE_FLOATS);
-    }
-}
-
-// ---- the channel forms of the two GEMM kernels (amp_scamp_trials_ch_run): row tile rb belongs to
-// channel rb / tpg (amp_trials.h channel_tile).  The kernel takes the channel's view of the
-// parameter block at its entry (its operators and band ranges), stages and guards its rows up to
-// the channel's limit, and runs the same gemm_tile call and epilogue: a row has the bits of its own
-// B = 1 forward with that channel, wherever in a tile it lies.  The stop counter is still compared
-// with E (P.B), and every other kernel of the iteration is per trial and runs as it is. ----
-
-__global__ __launch_bounds__(AMP_WG) void tscamp_ka_ch(ScampK P, ScampTrials R, TrialChannels CH, int t) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ int s_stop[GBM];
-    const GemmTile tile = xcd_tile();
-    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const ChannelTile ct = ch.tile(tile.rb, P.B);
     const int row0 = ct.row0, col0 = tile.cb * 128;
-    if (*R.nstop >= (unsigned)P.B) return;
-    if (!tile_rows_live(P.iters, row0, ct.lim, s_stop)) return;
-    P.WA += (size_t)ct.g * CH.wstride[0];
-    if (P.bandA) P.bandA += (size_t)ct.g * CH.bstride[0];
+    if (!tscamp_enter(P, R, ch, ct, 0, P.WA, P.bandA, s_stop)) return;
     const int twoN = 2 * P.N;
     const int kb = P.bandA ? P.bandA[2 * tile.cb] : 0, ke = P.bandA ? P.bandA[2 * tile.cb + 1] : -1;
     gemm_tile<128, ALoadPlain, 256>(ALoadPlain{P.xm, twoN, ct.lim, twoN}, P.WA, P.kapA, row0, col0, lds, kb, ke);
     scamp_residual<256>(P, LiveRows{s_stop}, t, lds, row0, col0);
 }
 
-template <int BN, int KK, int KC>
-__global__ __launch_bounds__(AMP_WG) void tscamp_kb_ch(ScampK P, ScampTrials R, TrialChannels CH, int t) {
+// scamp_kb, the denoiser and the in-tile psi row by row: each live row's own partial, in the slot
+// its B = 1 forward stores it to, from scratch past the C tile (LiveRows::PSCR: later rows still
+// read the tile and the tau tile)
+template <int BN, int KK, int KC, class CH>
+__global__ __launch_bounds__(AMP_WG) void tscamp_kb(ScampK P, ScampTrials R, CH ch, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_stop[GBM];
     using C = GemmCfg<BN, KC>;
     const GemmTile tile = xcd_tile();
-    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
+    const ChannelTile ct = ch.tile(tile.rb, P.B);
     const int row0 = ct.row0, col0 = tile.cb * BN;
-    if (*R.nstop >= (unsigned)P.B) return;
-    if (!tile_rows_live(P.iters, row0, ct.lim, s_stop)) return;
-    P.WAH += (size_t)ct.g * CH.wstride[1];
-    if (P.bandB) P.bandB += (size_t)ct.g * CH.bstride[1];
+    if (!tscamp_enter(P, R, ch, ct, 1, P.WAH, P.bandB, s_stop)) return;
     const int sld = scamp_sld(P.n);
     const int kb = P.bandB ? P.bandB[2 * tile.cb] : 0, ke = P.bandB ? P.bandB[2 * tile.cb + 1] : -1;
     gemm_tile<BN, ALoadPlain, KC>(ALoadPlain{P.s, sld, ct.lim, sld}, P.WAH, P.kapB, row0, col0, lds, kb, ke);
@@ -312,40 +274,27 @@ static int tscamp_attrs() {
     std::call_once(g_tscamp_once, [] {
         for (int K : {1, 2, 4, 8, 16, 64})
             dispatch_K(K, [](auto kk) {
-                if (!g_tscamp_rc) g_tscamp_rc = set_lds_attr<256>((const void*)tscamp_kb<256, decltype(kk)::value, GKC>);
+                constexpr int KK = decltype(kk)::value;
+                if (!g_tscamp_rc) g_tscamp_rc = set_lds_attr<256>((const void*)tscamp_kb<256, KK, GKC, OneChannel>);
+                if (!g_tscamp_rc) g_tscamp_rc = set_lds_attr<256>((const void*)tscamp_kb<256, KK, GKC, TrialChannels>);
             });
     });
     return g_tscamp_rc;
 }
 
-template <int KK>
-static void tscamp_launch_kb(const ScampK& P, const ScampTrials& R, int gr, int t, hipStream_t st) {
+template <int KK, class CH>
+static void tscamp_launch_kb(const ScampK& P, const ScampTrials& R, const CH& ch, int gr, int t, hipStream_t st) {
     if (P.bn == 128)
-        hipLaunchKernelGGL((tscamp_kb<128, KK, 256>), dim3(gr, P.ncpB / 128), dim3(AMP_WG), TS_LDS_S, st, P, R, t);
+        hipLaunchKernelGGL((tscamp_kb<128, KK, 256, CH>), dim3(gr, P.ncpB / 128), dim3(AMP_WG), TS_LDS_S, st, P, R, ch, t);
     else
-        hipLaunchKernelGGL((tscamp_kb<256, KK, GKC>), dim3(gr, P.ncpB / 256), dim3(AMP_WG), TS_LDS_W, st, P, R, t);
+        hipLaunchKernelGGL((tscamp_kb<256, KK, GKC, CH>), dim3(gr, P.ncpB / 256), dim3(AMP_WG), TS_LDS_W, st, P, R, ch, t);
 }
 
-static std::once_flag g_tscamp_ch_once;
-static int g_tscamp_ch_rc = 0;
-static int tscamp_ch_attrs() {
-    std::call_once(g_tscamp_ch_once, [] {
-        for (int K : {1, 2, 4, 8, 16, 64})
-            dispatch_K(K, [](auto kk) {
-                if (!g_tscamp_ch_rc)
-                    g_tscamp_ch_rc = set_lds_attr<256>((const void*)tscamp_kb_ch<256, decltype(kk)::value, GKC>);
-            });
-    });
-    return g_tscamp_ch_rc;
-}
-
-template <int KK>
-static void tscamp_launch_kb_ch(const ScampK& P, const ScampTrials& R, const TrialChannels& CH, int gr, int t,
-                                hipStream_t st) {
-    if (P.bn == 128)
-        hipLaunchKernelGGL((tscamp_kb_ch<128, KK, 256>), dim3(gr, P.ncpB / 128), dim3(AMP_WG), TS_LDS_S, st, P, R, CH, t);
-    else
-        hipLaunchKernelGGL((tscamp_kb_ch<256, KK, GKC>), dim3(gr, P.ncpB / 256), dim3(AMP_WG), TS_LDS_W, st, P, R, CH, t);
+// iteration t's two GEMM launches over gr row tiles
+template <class CH>
+static void tscamp_launch_gemms(const ScampK& P, const ScampTrials& R, const CH& ch, int gr, int t, hipStream_t st) {
+    hipLaunchKernelGGL(tscamp_ka<CH>, dim3(gr, P.ncpA / 128), dim3(AMP_WG), TS_LDS_S, st, P, R, ch, t);
+    dispatch_K(P.c.K, [&](auto kk) { tscamp_launch_kb<decltype(kk)::value>(P, R, ch, gr, t, st); });
 }
 
 // The operators of G channels (A: c64 [G][n][N]) and their band ranges, each channel's own, in a
@@ -367,111 +316,33 @@ static bool tscamp_shape_ok(const amp_dims* d, int E) {
            d->N == d->Nt * d->Lin && d->n == d->Nr * d->Lout && scamp_index_ok(d, E);
 }
 
-}  // namespace amp
-
-using namespace amp;
-
-extern "C" {
-
-size_t amp_scamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials) {
-    if (!d || max_iter <= 0 || trials <= 0 || d->B != 1 || !tscamp_shape_ok(d, trials)) return 0;
-    return tscamp_carve(d, trials, nullptr).bytes;
-}
-
-int amp_scamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
-                         const amp_trials_decide_args* dec, int32_t trials, void* stream) {
+// Both entries.  fn: the entry that was called (amp_scamp_trials_run passes per_channel = trials:
+// one channel); a->A holds the G = ceil(trials / per_channel) channels in order.
+static int tscamp_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
+                      const amp_trials_decide_args* dec, int trials, int per_channel, const char* fn, hipStream_t st) {
     int rc = check_dims(d, c, true, true);   // any Nt, a partial last column tile (amp_scamp_run)
     if (rc) return rc;
-    AMP_REQUIRE(d->B == 1, "amp_scamp_trials_run: dims describe ONE trial (B = %d, must be 1)", d->B);
-    AMP_REQUIRE(trials >= 1, "amp_scamp_trials_run: trials = %d", trials);
+    AMP_REQUIRE(d->B == 1, "%s: dims describe ONE trial (B = %d, must be 1)", fn, d->B);
+    AMP_REQUIRE(trials >= 1, "%s: trials = %d", fn, trials);
+    AMP_REQUIRE(per_channel >= 1, "%s: per_channel = %d", fn, per_channel);
     AMP_REQUIRE(a && a->W && a->A && a->y && a->xmap && a->xmmse && a->psi && a->status && a->ws,
-                "amp_scamp_trials_run: null pointer argument");
-    AMP_REQUIRE(a->max_iter > 0, "amp_scamp_trials_run: max_iter must be positive");
-    AMP_REQUIRE(d->Lin <= SMAXLIN, "amp_scamp_trials_run: Lin = %d > %d", d->Lin, SMAXLIN);
-    AMP_REQUIRE(scamp_index_ok(d, trials), "amp_scamp_trials_run: %d trials of max(2N, 2n) = %d columns need more "
-                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
-    AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES,
-                "amp_scamp_trials_run: launch engine only (engine %d)", a->engine);
-    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "amp_scamp_trials_run: f32 GEMMs only (gemm %d)",
-                a->gemm);
-    const int E = trials;
-    const TScampWs w = tscamp_carve(d, E, a->ws);
-    AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_scamp_trials_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
-    TrialsDecide td{};
-    if (dec && (rc = trials_decide_args(d, dec, a->xmap, a->xmmse, td))) return rc;
-    if ((rc = tscamp_attrs())) return rc;
-    ScampK P{};            // f32 tiles (lx3 = 0); the persistent engine's fields stay null
-    scamp_geometry(d, E, P);
-    P.max_iter = a->max_iter;
-    P.sigma2 = (float)a->noise_var;
-    P.W = (const float*)a->W;
-    P.WA = w.WA; P.WAH = w.WAH;
-    P.y = (const float*)a->y; P.z = w.z; P.s = w.s; P.phi = w.phi; P.tau = w.tau;
-    P.xmap = (float*)a->xmap; P.xm = (float*)a->xmmse; P.psi0 = (float*)a->psi; P.psi1 = w.psi1;
-    P.secmax = w.secmax; P.secabs = w.secabs; P.parts = w.parts;
-    P.iters = w.iters;
-    P.status = (amp_status*)a->status;
-    const bool band = d->Lin > 1 || d->Lout > 1;   // block-banded A (channel.py:75-95)
-    P.bandA = band ? w.bandA : nullptr;
-    P.bandB = band ? w.bandB : nullptr;
-    P.c = to_const(c);
-    const ScampTrials R{w.nstop, w.fixcnt, w.psi_nc};
-    const Const64 c64 = to_const64(c);
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = scamp_pack_f32(P, (const float2*)a->A, st))) return rc;   // the operators, packed once per call
-    const size_t tot = std::max(std::max((size_t)E * P.N, (size_t)E * P.n), (size_t)E * std::max(P.Lout, P.Lin));
-    hipLaunchKernelGGL(tscamp_init_kernel, dim3((int)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, P, R);
-    AMP_LAUNCH_CHECK("tscamp_init");
-    const int gr = cdiv(E, GBM);
-    const int npsi = std::max(1, std::min(cdiv(E * P.Lin, AMP_WG / 64), 2048));
-    for (int t = 0; t < P.max_iter; ++t) {
-        hipLaunchKernelGGL(tscamp_ka, dim3(gr, P.ncpA / 128), dim3(AMP_WG), TS_LDS_S, st, P, R, t);
-        dispatch_K(P.c.K, [&](auto kk) { tscamp_launch_kb<decltype(kk)::value>(P, R, gr, t, st); });
-        if (P.psi_split) hipLaunchKernelGGL(tscamp_psi, dim3(npsi), dim3(AMP_WG), 0, st, P, R, t);
-        hipLaunchKernelGGL(tscamp_r, dim3(E), dim3(TSRWG), 0, st, P, R, c64, t);
-        hipLaunchKernelGGL(tscamp_fix_sec, dim3(E), dim3(TSRWG), 0, st, P, R, c64, t);
-        hipLaunchKernelGGL(tscamp_fix_psi_fin, dim3(E), dim3(TSRWG), 0, st, P, R, t);
-        AMP_LAUNCH_CHECK("tscamp iteration");
-    }
-    hipLaunchKernelGGL(tscamp_output_kernel, dim3(E), dim3(64), 0, st, P);
-    AMP_LAUNCH_CHECK("tscamp_output");
-    return dec ? trials_decide_launch(d, c, td, E, w.dec, st) : AMP_OK;
-}
-
-size_t amp_scamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel) {
-    if (!d || max_iter <= 0 || trials <= 0 || per_channel < 1 || d->B != 1 || !tscamp_shape_ok(d, trials)) return 0;
-    int per = per_channel;
-    const int G = trial_channels(trials, per);
-    if (G > WCH_MAX) return 0;
-    return tscamp_carve(d, trials, nullptr, G).bytes;
-}
-
-int amp_scamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
-                            const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
-    int rc = check_dims(d, c, true, true);   // any Nt, a partial last column tile (amp_scamp_run)
-    if (rc) return rc;
-    AMP_REQUIRE(d->B == 1, "amp_scamp_trials_ch_run: dims describe ONE trial (B = %d, must be 1)", d->B);
-    AMP_REQUIRE(trials >= 1, "amp_scamp_trials_ch_run: trials = %d", trials);
-    AMP_REQUIRE(per_channel >= 1, "amp_scamp_trials_ch_run: per_channel = %d", per_channel);
-    AMP_REQUIRE(a && a->W && a->A && a->y && a->xmap && a->xmmse && a->psi && a->status && a->ws,
-                "amp_scamp_trials_ch_run: null pointer argument");
-    AMP_REQUIRE(a->max_iter > 0, "amp_scamp_trials_ch_run: max_iter must be positive");
-    AMP_REQUIRE(d->Lin <= SMAXLIN, "amp_scamp_trials_ch_run: Lin = %d > %d", d->Lin, SMAXLIN);
-    AMP_REQUIRE(scamp_index_ok(d, trials), "amp_scamp_trials_ch_run: %d trials of max(2N, 2n) = %d columns need more "
-                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
-    AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES,
-                "amp_scamp_trials_ch_run: launch engine only (engine %d)", a->engine);
-    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "amp_scamp_trials_ch_run: f32 GEMMs only (gemm %d)",
-                a->gemm);
+                "%s: null pointer argument", fn);
+    AMP_REQUIRE(a->max_iter > 0, "%s: max_iter must be positive", fn);
+    AMP_REQUIRE(d->Lin <= SMAXLIN, "%s: Lin = %d > %d", fn, d->Lin, SMAXLIN);
+    AMP_REQUIRE(scamp_index_ok(d, trials), "%s: %d trials of max(2N, 2n) = %d columns need more than 32-bit offsets "
+                "(or more than 65535 column tiles)", fn, trials, 2 * std::max(d->N, d->n));
+    AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES, "%s: launch engine only (engine %d)",
+                fn, a->engine);
+    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "%s: f32 GEMMs only (gemm %d)", fn, a->gemm);
     const int E = trials;
     int per = per_channel;
     const int G = trial_channels(E, per);
-    AMP_REQUIRE(G <= WCH_MAX, "amp_scamp_trials_ch_run: %d channels (at most %d per call: a grid axis)", G, WCH_MAX);
+    AMP_REQUIRE(G <= WCH_MAX, "%s: %d channels (at most %d per call: a grid axis)", fn, G, WCH_MAX);
     const TScampWs w = tscamp_carve(d, E, a->ws, G);
-    AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_scamp_trials_ch_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
+    AMP_REQUIRE(a->ws_bytes >= w.bytes, "%s: workspace %zu < %zu bytes", fn, a->ws_bytes, w.bytes);
     TrialsDecide td{};
     if (dec && (rc = trials_decide_args(d, dec, a->xmap, a->xmmse, td))) return rc;
-    if ((rc = tscamp_ch_attrs())) return rc;
+    if ((rc = tscamp_attrs())) return rc;
     ScampK P{};            // f32 tiles (lx3 = 0); the persistent engine's fields stay null
     scamp_geometry(d, E, P);
     P.max_iter = a->max_iter;
@@ -494,25 +365,55 @@ int amp_scamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const
     CH.bstride[1] = G == 1 ? 2 * (P.ncpB / P.bn) : band_stride(P.ncpB / P.bn);
     const ScampTrials R{w.nstop, w.fixcnt, w.psi_nc};
     const Const64 c64 = to_const64(c);
-    hipStream_t st = (hipStream_t)stream;
     if ((rc = tscamp_pack_ch(P, CH, (const float2*)a->A, G, st))) return rc;   // every channel's operators, once per call
     const size_t tot = std::max(std::max((size_t)E * P.N, (size_t)E * P.n), (size_t)E * std::max(P.Lout, P.Lin));
     hipLaunchKernelGGL(tscamp_init_kernel, dim3((int)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, P, R);
     AMP_LAUNCH_CHECK("tscamp_init");
-    const int gr = G * CH.tpg;                     // <= E row tiles
+    const int gr = G * CH.tpg;                     // <= E row tiles; one channel: cdiv(E, 32)
     const int npsi = std::max(1, std::min(cdiv(E * P.Lin, AMP_WG / 64), 2048));
     for (int t = 0; t < P.max_iter; ++t) {
-        hipLaunchKernelGGL(tscamp_ka_ch, dim3(gr, P.ncpA / 128), dim3(AMP_WG), TS_LDS_S, st, P, R, CH, t);
-        dispatch_K(P.c.K, [&](auto kk) { tscamp_launch_kb_ch<decltype(kk)::value>(P, R, CH, gr, t, st); });
+        if (G == 1)
+            tscamp_launch_gemms(P, R, OneChannel{}, gr, t, st);
+        else
+            tscamp_launch_gemms(P, R, CH, gr, t, st);
         if (P.psi_split) hipLaunchKernelGGL(tscamp_psi, dim3(npsi), dim3(AMP_WG), 0, st, P, R, t);
         hipLaunchKernelGGL(tscamp_r, dim3(E), dim3(TSRWG), 0, st, P, R, c64, t);
         hipLaunchKernelGGL(tscamp_fix_sec, dim3(E), dim3(TSRWG), 0, st, P, R, c64, t);
         hipLaunchKernelGGL(tscamp_fix_psi_fin, dim3(E), dim3(TSRWG), 0, st, P, R, t);
-        AMP_LAUNCH_CHECK("tscamp_ch iteration");
+        AMP_LAUNCH_CHECK("tscamp iteration");
     }
     hipLaunchKernelGGL(tscamp_output_kernel, dim3(E), dim3(64), 0, st, P);
     AMP_LAUNCH_CHECK("tscamp_output");
     return dec ? trials_decide_launch(d, c, td, E, w.dec, st) : AMP_OK;
+}
+
+}  // namespace amp
+
+using namespace amp;
+
+extern "C" {
+
+size_t amp_scamp_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials) {
+    if (!d || max_iter <= 0 || trials <= 0 || d->B != 1 || !tscamp_shape_ok(d, trials)) return 0;
+    return tscamp_carve(d, trials, nullptr).bytes;
+}
+
+int amp_scamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
+                         const amp_trials_decide_args* dec, int32_t trials, void* stream) {
+    return tscamp_run(d, c, a, dec, trials, trials, "amp_scamp_trials_run", (hipStream_t)stream);
+}
+
+size_t amp_scamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel) {
+    if (!d || max_iter <= 0 || trials <= 0 || per_channel < 1 || d->B != 1 || !tscamp_shape_ok(d, trials)) return 0;
+    int per = per_channel;
+    const int G = trial_channels(trials, per);
+    if (G > WCH_MAX) return 0;
+    return tscamp_carve(d, trials, nullptr, G).bytes;
+}
+
+int amp_scamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
+                            const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
+    return tscamp_run(d, c, a, dec, trials, per_channel, "amp_scamp_trials_ch_run", (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -46,26 +46,40 @@ __device__ __forceinline__ bool tile_rows_live(const REC* recs, int row0, int ro
     return live != 0;
 }
 
-// Several channels per trial batch (amp_bamp_trials_ch_run / amp_scamp_trials_ch_run): trial e uses
-// channel e / per, so channel g owns rows [g per, min((g + 1) per, E)) and tpg = ceil(per / 32) row
-// tiles of the grid; row tile rb belongs to channel rb / tpg and starts at row g per + (rb % tpg) 32
-// (no multiple of 32 in general, and possibly odd).  `lim`, the channel's last row + 1, is the row
-// limit of the tile's A loader and of tile_rows_live: rows of the next channel that fall inside the
-// 32-row tile are staged as zeros and marked stopped, so they are neither multiplied with this
-// channel's operator nor stored.  wstride / bstride: floats / ints between two channels' packed
-// operators / band ranges (per GEMM operator of the engine).
+// The channel mapping of a trial batch, the policy every trial GEMM kernel is written over (one
+// kernel family; the host launches the OneChannel instantiation for one channel, TrialChannels for
+// several).  Trial e uses channel e / per, so channel g owns rows [g per, min((g + 1) per, E)) and
+// tpg = ceil(per / 32) row tiles of the grid; row tile rb belongs to channel rb / tpg and starts at
+// row g per + (rb % tpg) 32 (no multiple of 32 in general, and possibly odd).  `lim`, the channel's
+// last row + 1, is the row limit of the tile's A loader and of tile_rows_live: rows of the next
+// channel that fall inside the 32-row tile are staged as zeros and marked stopped, so they are
+// neither multiplied with this channel's operator nor stored.  wstride / bstride: floats / ints
+// between two channels' packed operators / band ranges (per GEMM operator of the engine).
+// Interface: tile(rb, E); of(e), trial e's channel; woff / boff(g, i), what steps operator i's
+// weights / band ranges to channel g.
+struct ChannelTile {
+    int g, row0, lim;
+};
 struct TrialChannels {
     int per, tpg;
     size_t wstride[4];
     int bstride[4];
+    __device__ __forceinline__ ChannelTile tile(int rb, int E) const {
+        const int g = rb / tpg;
+        return ChannelTile{g, g * per + (rb - g * tpg) * GBM, min((g + 1) * per, E)};
+    }
+    __device__ __forceinline__ int of(int e) const { return e / per; }
+    __device__ __forceinline__ size_t woff(int g, int i) const { return (size_t)g * wstride[i]; }
+    __device__ __forceinline__ size_t boff(int g, int i) const { return (size_t)g * bstride[i]; }
 };
-struct ChannelTile {
-    int g, row0, lim;
+// One channel: every row tile is channel 0's, the row limit is E and no pointer moves; the constants
+// fold, so a kernel's instantiation does the work of a kernel written for one channel.
+struct OneChannel {
+    __device__ __forceinline__ ChannelTile tile(int rb, int E) const { return ChannelTile{0, rb * GBM, E}; }
+    __device__ __forceinline__ int of(int) const { return 0; }
+    __device__ __forceinline__ size_t woff(int, int) const { return 0; }
+    __device__ __forceinline__ size_t boff(int, int) const { return 0; }
 };
-__device__ __forceinline__ ChannelTile channel_tile(const TrialChannels& C, int rb, int E) {
-    const int g = rb / C.tpg;
-    return ChannelTile{g, g * C.per + (rb - g * C.tpg) * GBM, min((g + 1) * C.per, E)};
-}
 // ints between two channels' band ranges of an operator with `ntiles` column tiles: whole 256-byte
 // workspace granules, so G channels cost exactly G times one channel's bytes
 inline int band_stride(int ntiles) { return (2 * ntiles + 63) & ~63; }

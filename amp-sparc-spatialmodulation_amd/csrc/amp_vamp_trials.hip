@@ -18,11 +18,13 @@
 // A row's GEMM result does not depend on the other rows of its tile (each MFMA output row reduces
 // its own A row only), so a trial's values are those of its own B = 1 forward on the launch engine.
 // amp_vamp_trials_ch_run: the same over G channels, trial e on channel e / per_channel
-// (vamp_model.py:45-61 redraws the channel every `res` epochs).  The channel forms tvamp_k1_ch /
-// tvamp_k2_ch / tvamp_r_ch take the channel's view of the parameter block at their entry (Wt1, Wt2,
-// s, s2 and the channel's last row as the row limit) and call the same bodies; y~ is gemm_store_ch
-// with each channel's Wt0, the iteration-0 record is one per channel, and the operators of all
-// channels are packed in three launches.
+// (vamp_model.py:45-61 redraws the channel every `res` epochs).  One kernel family serves both
+// entries: tvamp_k1 / tvamp_k2 / tvamp_r are templates over the channel mapping (amp_trials.h:
+// OneChannel where the call has one channel, TrialChannels for several) and take the channel's view
+// of the parameter block at their entry (Wt1, Wt2, s, s2 and the channel's last row as the row
+// limit); one host function runs either; y~ is gemm_store_ch with each channel's Wt0, the
+// iteration-0 record is one per channel, and the operators of all channels are packed in three
+// launches.
 #include <algorithm>
 #include <mutex>
 
@@ -40,11 +42,11 @@ struct TVampWs {
 };
 
 // floats between two channels' s2 in a workspace of G channels: whole 256-byte granules, so G
-// channels cost exactly G times one channel's bytes (one channel: the dense k of amp_vamp_trials_run)
+// channels cost exactly G times one channel's bytes (one channel: the dense k)
 inline size_t tvamp_s2_stride(int k, int G) { return G == 1 ? (size_t)k : (size_t)round_up(k, 64); }
 
-// G: channels whose packed operators and s2 the workspace holds (amp_vamp_trials_ch_run; one
-// channel: the layout and bytes of amp_vamp_trials_run)
+// G: channels whose packed operators and s2 the workspace holds (one channel: the bytes
+// amp_vamp_trials_workspace_bytes answers)
 static TVampWs tvamp_carve(const amp_dims* d, int k, int E, void* base, int G = 1) {
     VampK P;
     vamp_geometry(d, k, P);
@@ -67,161 +69,17 @@ static TVampWs tvamp_carve(const amp_dims* d, int k, int E, void* base, int G = 
     return w;
 }
 
-// Tracker (vamp.py:22-26) for every trial, and every trial's iteration-0 record (the same: it
-// depends on the channel and the SNR only).
-__global__ __launch_bounds__(256) void tvamp_init_kernel(VampK P, unsigned* nstop) {
-    __shared__ __attribute__((aligned(16))) float lds[64];
-    vamp_init_state(P);
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) *nstop = 0u;
-        const VampIter it = vamp_first_iter(P, lds);
-        for (int e = threadIdx.x; e < P.B; e += blockDim.x) P.iters[e] = it;
-    }
-}
+// The channel mapping CH (amp_trials.h) of the kernels below.  CH.wstride: floats between two
+// channels' Wt0 / Wt1 / Wt2 / s2; the singular values lie dense, k apart.  A kernel takes the
+// channel's view of its by-value P at the entry and calls the launch engine's bodies: a row has the
+// bits of its own B = 1 forward with that channel, wherever in a tile it lies (every row stride is
+// even: no alignment changes with a first row that is no multiple of 32, or odd).
 
-__global__ __launch_bounds__(AMP_WG) void tvamp_k1(VampK P, const unsigned* nstop) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ VampIter s_it[GBM];
-    if (*nstop >= (unsigned)P.B) return;
-    const GemmTile tile = xcd_tile();
-    const int row0 = tile.rb * GBM, col0 = tile.cb * 128;
-    if (!vamp_tile_records(P.iters, row0, P.B, s_it)) return;
-    const VampLiveRows g{s_it};
-    gemm_tile<128>(vamp_aload_rt(P, g, row0), P.Wt1, P.kap1, row0, col0, lds);
-    vamp_lmmse_epilogue(P, g, lds, row0, col0);
-}
-
-template <int BN, int KK>
-__global__ __launch_bounds__(AMP_WG) void tvamp_k2(VampK P, int t, const unsigned* nstop) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ VampIter s_it[GBM];
-    if (*nstop >= (unsigned)P.B) return;
-    const GemmTile tile = xcd_tile();
-    const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    if (!vamp_tile_records(P.iters, row0, P.B, s_it)) return;
-    const VampLiveRows g{s_it};
-    gemm_tile<BN>(ALoadPlain{P.w, P.wld, P.B, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
-    const int nrows = min(GBM, P.B - row0), ncols = min(BN, 2 * P.N - col0);
-    vamp_r_epilogue<BN>(P, g, lds, row0, col0, nrows, ncols);
-    // the denoiser row by row, the row's own partial in the slot its B = 1 forward stores it to
-    // (s_it is workgroup-uniform: no divergent barrier)
-    const int nct = P.ncp2 / BN, slot = seq_part_slot(tile.cb, nct);
-    for (int rho = 0; rho < nrows; ++rho) {
-        if (!g.live(rho)) continue;
-        const VampDenoisePolicy pol = vamp_policy<BN>(P, g, t, lds, row0, col0, ncols, rho);
-        PartAcc pa;
-        denoise_sections<true, KK>(pol, pol.spr, P.M, P.c, pa);
-        part_block_store(pa, P.parts + (size_t)(row0 + rho) * nct + slot, lds + GemmCfg<BN>::CTILE_FLOATS);
-    }
-}
-struct TVampK2 {
-    template <int BN, int KK>
-    static constexpr auto fn() { return &tvamp_k2<BN, KK>; }
-};
-
-// Workgroup e after K2(t): vamp_r (amp_vamp.hip) on trial e's rows, every trial in parallel.
-__global__ __launch_bounds__(RWG) void tvamp_r(VampK PE, Const64 c64, int t, unsigned* nstop) {
-    __shared__ __attribute__((aligned(16))) float lds[512];
-    if (*nstop >= (unsigned)PE.B) return;
-    const int e = blockIdx.x;
-    const VampIter cur = PE.iters[e];
-    if (cur.stopped) return;
-    // the trial as a batch of one
-    VampK P = PE;
-    const int nct = PE.ncp2 / PE.bn2;
-    P.B = 1; P.Bmean = 1;
-    P.r = PE.r + (size_t)e * 2 * PE.N; P.xm = PE.xm + (size_t)e * 2 * PE.N;
-    P.var0 = PE.var0 + (size_t)e * PE.N; P.var1 = PE.var1 + (size_t)e * PE.N;
-    P.secmax = PE.secmax + (size_t)e * PE.L; P.secabs = PE.secabs + (size_t)e * PE.L;
-    P.parts = PE.parts + (size_t)e * nct;
-    const VampIter nx = vamp_reduce(P, c64, cur, P.parts, nct, &PE.iters[e], &PE.status[e], t, lds);
-    if (threadIdx.x == 0 && nx.stopped) __hip_atomic_fetch_add(nstop, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- the channel forms (amp_vamp_trials_ch_run): row tile rb belongs to channel rb / tpg
-// (amp_trials.h channel_tile).  CH.wstride: floats between two channels' Wt0 / Wt1 / Wt2 / s2; the
-// singular values lie dense, k apart.  A kernel takes the channel's view of its by-value P at the
-// entry and runs the one-channel kernel's calls: a row has the bits of its own B = 1 forward with
-// that channel, wherever in a tile it lies (every row stride is even: no alignment changes with a
-// first row that is no multiple of 32, or odd). ----
-
-// false (workgroup-uniform) when every trial has stopped or no row of the tile is live; else s_it
-// holds the tile's records (rows of the next channel as stopped) and P is channel ct.g's: its
-// operators and s2, and its last row + 1 as the row limit of the loaders and epilogues (P.B)
-__device__ __forceinline__ bool tvamp_ch_enter(VampK& P, const TrialChannels& CH, const ChannelTile& ct,
-                                               const unsigned* nstop, VampIter* s_it) {
-    if (*nstop >= (unsigned)P.B) return false;
-    if (!vamp_tile_records(P.iters, ct.row0, ct.lim, s_it)) return false;
-    P.Wt1 += (size_t)ct.g * CH.wstride[1];
-    P.Wt2 += (size_t)ct.g * CH.wstride[2];
-    P.s2 += (size_t)ct.g * CH.wstride[3];
-    P.s += (size_t)ct.g * P.k;
-    P.B = ct.lim;
-    return true;
-}
-
-__global__ __launch_bounds__(AMP_WG) void tvamp_k1_ch(VampK P, TrialChannels CH, const unsigned* nstop) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ VampIter s_it[GBM];
-    const GemmTile tile = xcd_tile();
-    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
-    const int row0 = ct.row0, col0 = tile.cb * 128;
-    if (!tvamp_ch_enter(P, CH, ct, nstop, s_it)) return;
-    const VampLiveRows g{s_it};
-    gemm_tile<128>(vamp_aload_rt(P, g, row0), P.Wt1, P.kap1, row0, col0, lds);
-    vamp_lmmse_epilogue(P, g, lds, row0, col0);
-}
-
-template <int BN, int KK>
-__global__ __launch_bounds__(AMP_WG) void tvamp_k2_ch(VampK P, TrialChannels CH, int t, const unsigned* nstop) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ VampIter s_it[GBM];
-    const GemmTile tile = xcd_tile();
-    const ChannelTile ct = channel_tile(CH, tile.rb, P.B);
-    const int row0 = ct.row0, col0 = tile.cb * BN;
-    if (!tvamp_ch_enter(P, CH, ct, nstop, s_it)) return;
-    const VampLiveRows g{s_it};
-    gemm_tile<BN>(ALoadPlain{P.w, P.wld, ct.lim, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
-    const int nrows = min(GBM, ct.lim - row0), ncols = min(BN, 2 * P.N - col0);
-    vamp_r_epilogue<BN>(P, g, lds, row0, col0, nrows, ncols);
-    const int nct = P.ncp2 / BN, slot = seq_part_slot(tile.cb, nct);
-    for (int rho = 0; rho < nrows; ++rho) {
-        if (!g.live(rho)) continue;   // workgroup-uniform
-        const VampDenoisePolicy pol = vamp_policy<BN>(P, g, t, lds, row0, col0, ncols, rho);
-        PartAcc pa;
-        denoise_sections<true, KK>(pol, pol.spr, P.M, P.c, pa);
-        part_block_store(pa, P.parts + (size_t)(row0 + rho) * nct + slot, lds + GemmCfg<BN>::CTILE_FLOATS);
-    }
-}
-struct TVampK2Ch {
-    template <int BN, int KK>
-    static constexpr auto fn() { return &tvamp_k2_ch<BN, KK>; }
-};
-
-// tvamp_r with trial e's channel: P.s at channel e / per's singular values (vamp_lmmse_scalars'
-// mean(scale), vamp.py:68-71)
-__global__ __launch_bounds__(RWG) void tvamp_r_ch(VampK PE, int per, Const64 c64, int t, unsigned* nstop) {
-    __shared__ __attribute__((aligned(16))) float lds[512];
-    if (*nstop >= (unsigned)PE.B) return;
-    const int e = blockIdx.x;
-    const VampIter cur = PE.iters[e];
-    if (cur.stopped) return;
-    VampK P = PE;
-    const int nct = PE.ncp2 / PE.bn2;
-    P.B = 1; P.Bmean = 1;
-    P.s = PE.s + (size_t)(e / per) * PE.k;
-    P.r = PE.r + (size_t)e * 2 * PE.N; P.xm = PE.xm + (size_t)e * 2 * PE.N;
-    P.var0 = PE.var0 + (size_t)e * PE.N; P.var1 = PE.var1 + (size_t)e * PE.N;
-    P.secmax = PE.secmax + (size_t)e * PE.L; P.secabs = PE.secabs + (size_t)e * PE.L;
-    P.parts = PE.parts + (size_t)e * nct;
-    const VampIter nx = vamp_reduce(P, c64, cur, P.parts, nct, &PE.iters[e], &PE.status[e], t, lds);
-    if (threadIdx.x == 0 && nx.stopped) __hip_atomic_fetch_add(nstop, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// tvamp_init_kernel for G channels: every channel's s2 and its own iteration-0 record
-// (vamp_first_iter sums 1 / (s_i^2 + vr) over the channel's singular values), written to the
-// channel's trials; the channels go grid-strided over the workgroups
-__global__ __launch_bounds__(256) void tvamp_init_ch_kernel(VampK P, TrialChannels CH, int G, unsigned* nstop) {
+// Tracker (vamp.py:22-26) for every trial, every channel's s2 and its own iteration-0 record
+// (vamp_first_iter sums 1 / (s_i^2 + vr) over the channel's singular values: it depends on the
+// channel and the SNR only), written to the channel's trials; the channels go grid-strided over the
+// workgroups.  Once per call, so one runtime form for any G.
+__global__ __launch_bounds__(256) void tvamp_init_kernel(VampK P, TrialChannels CH, int G, unsigned* nstop) {
     __shared__ __attribute__((aligned(16))) float lds[64];
     vamp_init_state(P);   // and channel 0's s2
     const size_t rest = (size_t)(G - 1) * P.k;
@@ -240,6 +98,88 @@ __global__ __launch_bounds__(256) void tvamp_init_ch_kernel(VampK P, TrialChanne
     }
 }
 
+// The entry of both GEMM kernels.  false (workgroup-uniform) when every trial has stopped or no row
+// of the tile is live; else s_it holds the tile's records (rows of the next channel as stopped) and
+// P is channel ct.g's: its operators, s and s2, and its last row + 1 as the row limit of the loaders
+// and epilogues (P.B).  The stop counter is compared with E whatever the channels.
+template <class CH>
+__device__ __forceinline__ bool tvamp_enter(VampK& P, const CH& ch, const ChannelTile& ct, const unsigned* nstop,
+                                            VampIter* s_it) {
+    if (*nstop >= (unsigned)P.B) return false;
+    if (!vamp_tile_records(P.iters, ct.row0, ct.lim, s_it)) return false;
+    P.Wt1 += ch.woff(ct.g, 1);
+    P.Wt2 += ch.woff(ct.g, 2);
+    P.s2 += ch.woff(ct.g, 3);
+    P.s += (size_t)ct.g * P.k;
+    P.B = ct.lim;
+    return true;
+}
+
+// GEMM1 over row tiles of 32 trials, each row's r~ and LMMSE epilogue with its own record
+template <class CH>
+__global__ __launch_bounds__(AMP_WG) void tvamp_k1(VampK P, CH ch, const unsigned* nstop) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ VampIter s_it[GBM];
+    const GemmTile tile = xcd_tile();
+    const ChannelTile ct = ch.tile(tile.rb, P.B);
+    const int row0 = ct.row0, col0 = tile.cb * 128;
+    if (!tvamp_enter(P, ch, ct, nstop, s_it)) return;
+    const VampLiveRows g{s_it};
+    gemm_tile<128>(vamp_aload_rt(P, g, row0), P.Wt1, P.kap1, row0, col0, lds);
+    vamp_lmmse_epilogue(P, g, lds, row0, col0);
+}
+
+template <int BN, int KK, class CH>
+__global__ __launch_bounds__(AMP_WG) void tvamp_k2(VampK P, CH ch, int t, const unsigned* nstop) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ VampIter s_it[GBM];
+    const GemmTile tile = xcd_tile();
+    const ChannelTile ct = ch.tile(tile.rb, P.B);
+    const int row0 = ct.row0, col0 = tile.cb * BN;
+    if (!tvamp_enter(P, ch, ct, nstop, s_it)) return;
+    const VampLiveRows g{s_it};
+    gemm_tile<BN>(ALoadPlain{P.w, P.wld, ct.lim, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
+    const int nrows = min(GBM, ct.lim - row0), ncols = min(BN, 2 * P.N - col0);
+    vamp_r_epilogue<BN>(P, g, lds, row0, col0, nrows, ncols);
+    // the denoiser row by row, the row's own partial in the slot its B = 1 forward stores it to
+    // (s_it is workgroup-uniform: no divergent barrier)
+    const int nct = P.ncp2 / BN, slot = seq_part_slot(tile.cb, nct);
+    for (int rho = 0; rho < nrows; ++rho) {
+        if (!g.live(rho)) continue;
+        const VampDenoisePolicy pol = vamp_policy<BN>(P, g, t, lds, row0, col0, ncols, rho);
+        PartAcc pa;
+        denoise_sections<true, KK>(pol, pol.spr, P.M, P.c, pa);
+        part_block_store(pa, P.parts + (size_t)(row0 + rho) * nct + slot, lds + GemmCfg<BN>::CTILE_FLOATS);
+    }
+}
+template <class CH>
+struct TVampK2 {
+    template <int BN, int KK>
+    static constexpr auto fn() { return &tvamp_k2<BN, KK, CH>; }
+};
+
+// Workgroup e after K2(t): vamp_r (amp_vamp.hip) on trial e's rows, every trial in parallel, with
+// P.s at the singular values of trial e's channel (vamp_lmmse_scalars' mean(scale), vamp.py:68-71).
+template <class CH>
+__global__ __launch_bounds__(RWG) void tvamp_r(VampK PE, CH ch, Const64 c64, int t, unsigned* nstop) {
+    __shared__ __attribute__((aligned(16))) float lds[512];
+    if (*nstop >= (unsigned)PE.B) return;
+    const int e = blockIdx.x;
+    const VampIter cur = PE.iters[e];
+    if (cur.stopped) return;
+    // the trial as a batch of one
+    VampK P = PE;
+    const int nct = PE.ncp2 / PE.bn2;
+    P.B = 1; P.Bmean = 1;
+    P.s = PE.s + (size_t)ch.of(e) * PE.k;
+    P.r = PE.r + (size_t)e * 2 * PE.N; P.xm = PE.xm + (size_t)e * 2 * PE.N;
+    P.var0 = PE.var0 + (size_t)e * PE.N; P.var1 = PE.var1 + (size_t)e * PE.N;
+    P.secmax = PE.secmax + (size_t)e * PE.L; P.secabs = PE.secabs + (size_t)e * PE.L;
+    P.parts = PE.parts + (size_t)e * nct;
+    const VampIter nx = vamp_reduce(P, c64, cur, P.parts, nct, &PE.iters[e], &PE.status[e], t, lds);
+    if (threadIdx.x == 0 && nx.stopped) __hip_atomic_fetch_add(nstop, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Trial e's last executed iteration wrote var into buffer (T_e - 1) & 1; buffer 0 is the caller's.
 __global__ __launch_bounds__(256) void tvamp_output_kernel(VampK P) {
     const int e = blockIdx.x;
@@ -253,34 +193,34 @@ static int g_tvamp_attr_rc = 0;
 
 static int tvamp_attrs() {
     std::call_once(g_tvamp_attr_once, [] {
-        const int rc = set_lds_attr<128>((const void*)tvamp_k1);
-        g_tvamp_attr_rc = rc ? rc : vamp_k2_attrs<TVampK2>();
+        int rc = set_lds_attr<128>((const void*)tvamp_k1<OneChannel>);
+        if (!rc) rc = set_lds_attr<128>((const void*)tvamp_k1<TrialChannels>);
+        if (!rc) rc = vamp_k2_attrs<TVampK2<OneChannel>>();
+        g_tvamp_attr_rc = rc ? rc : vamp_k2_attrs<TVampK2<TrialChannels>>();
     });
     return g_tvamp_attr_rc;
 }
 
-static std::once_flag g_tvamp_ch_attr_once;
-static int g_tvamp_ch_attr_rc = 0;
-
-static int tvamp_ch_attrs() {
-    std::call_once(g_tvamp_ch_attr_once, [] {
-        const int rc = set_lds_attr<128>((const void*)tvamp_k1_ch);
-        g_tvamp_ch_attr_rc = rc ? rc : vamp_k2_attrs<TVampK2Ch>();
-    });
-    return g_tvamp_ch_attr_rc;
-}
-
-// vamp_k2_launch over gr = G * tpg row tiles
-static void tvamp_k2_ch_launch(const VampK& P, const TrialChannels& CH, int gr, int t, const unsigned* nstop,
-                               hipStream_t st) {
-    const dim3 g2(gr, P.ncp2 / P.bn2);
+// iteration t's three launches: K1 and K2 over gr row tiles, tvamp_r over the E trials
+template <class CH>
+static int tvamp_launch_iter(const VampK& P, const CH& ch, const Const64& c64, int gr, int t, unsigned* nstop,
+                             hipStream_t st) {
+    const dim3 g1(gr, P.ncp1 / 128), g2(gr, P.ncp2 / P.bn2);
+    hipLaunchKernelGGL(tvamp_k1<CH>, g1, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, ch, (const unsigned*)nstop);
+    AMP_LAUNCH_CHECK("tvamp_k1");
     dispatch_K(P.c.K, [&](auto kk) {
         constexpr int KK = decltype(kk)::value;
         if (P.bn2 == 128)
-            hipLaunchKernelGGL((tvamp_k2_ch<128, KK>), g2, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, CH, t, nstop);
+            hipLaunchKernelGGL((tvamp_k2<128, KK, CH>), g2, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, ch, t,
+                               (const unsigned*)nstop);
         else
-            hipLaunchKernelGGL((tvamp_k2_ch<256, KK>), g2, dim3(AMP_WG), GemmCfg<256>::LDS_BYTES, st, P, CH, t, nstop);
+            hipLaunchKernelGGL((tvamp_k2<256, KK, CH>), g2, dim3(AMP_WG), GemmCfg<256>::LDS_BYTES, st, P, ch, t,
+                               (const unsigned*)nstop);
     });
+    AMP_LAUNCH_CHECK("tvamp_k2");
+    hipLaunchKernelGGL(tvamp_r<CH>, dim3(P.B), dim3(RWG), 0, st, P, ch, c64, t, nstop);
+    AMP_LAUNCH_CHECK("tvamp_r");
+    return AMP_OK;
 }
 
 // vamp_pack_f32 for G channels (a->U c64 [G][n][k], a->s f32 [G][k], a->Vh c64 [G][k][N]), each
@@ -298,116 +238,35 @@ static int vamp_pack_f32_ch(const VampK& P, const TrialChannels& CH, const amp_v
                             G, st);
 }
 
-}  // namespace amp
-
-using namespace amp;
-
-extern "C" {
-
-size_t amp_vamp_trials_workspace_bytes(const amp_dims* d, int32_t k, int32_t max_iter, int32_t trials) {
-    if (!d || k <= 0 || max_iter <= 0 || trials <= 0 || d->B != 1) return 0;
-    return tvamp_carve(d, k, trials, nullptr).bytes;
-}
-
-int amp_vamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
-                        const amp_trials_decide_args* dec, int32_t trials, void* stream) {
+// Both entries.  fn: the entry that was called (amp_vamp_trials_run passes per_channel = trials: one
+// channel); a->U / a->s / a->Vh hold the G = ceil(trials / per_channel) channels in order.
+static int tvamp_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
+                     const amp_trials_decide_args* dec, int trials, int per_channel, const char* fn, hipStream_t st) {
     int rc = check_dims(d, c, true, true);   // any n, any k, any even N, a partial last column tile (amp_vamp_run)
     if (rc) return rc;
-    AMP_REQUIRE(d->B == 1, "amp_vamp_trials_run: dims describe ONE trial (B = %d, must be 1)", d->B);
-    AMP_REQUIRE(trials >= 1, "amp_vamp_trials_run: trials = %d", trials);
-    AMP_REQUIRE(vamp_index_ok(d, trials), "amp_vamp_trials_run: %d trials of max(2N, 2n) = %d columns need more "
-                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
-    AMP_REQUIRE(a && a->U && a->s && a->Vh && a->y && a->r && a->xmmse && a->var && a->status && a->ws,
-                "amp_vamp_trials_run: null pointer argument");
-    AMP_REQUIRE(a->k > 0 && a->k <= d->N && a->k <= d->n, "amp_vamp_trials_run: k = %d must be min(n, N)", a->k);
-    AMP_REQUIRE(a->max_iter > 0, "amp_vamp_trials_run: max_iter must be positive");
-    AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES,
-                "amp_vamp_trials_run: the persistent engine has no independent-trial form");
-    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "amp_vamp_trials_run: f32 GEMMs only (gemm %d)",
-                a->gemm);
+    AMP_REQUIRE(d->B == 1, "%s: dims describe ONE trial (B = %d, must be 1)", fn, d->B);
+    AMP_REQUIRE(trials >= 1, "%s: trials = %d", fn, trials);
+    AMP_REQUIRE(per_channel >= 1, "%s: per_channel = %d", fn, per_channel);
+    AMP_REQUIRE(vamp_index_ok(d, trials), "%s: %d trials of max(2N, 2n) = %d columns need more than 32-bit offsets "
+                "(or more than 65535 column tiles)", fn, trials, 2 * std::max(d->N, d->n));
     const int E = trials;
-    const TVampWs w = tvamp_carve(d, a->k, E, a->ws);
-    AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_vamp_trials_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
+    int per = per_channel;
+    const int G = trial_channels(E, per);
+    AMP_REQUIRE(G <= WCH_MAX, "%s: %d channels (at most %d per call: a grid axis)", fn, G, WCH_MAX);
+    AMP_REQUIRE(a && a->U && a->s && a->Vh && a->y && a->r && a->xmmse && a->var && a->status && a->ws,
+                "%s: null pointer argument", fn);
+    AMP_REQUIRE(a->k > 0 && a->k <= d->N && a->k <= d->n, "%s: k = %d must be min(n, N)", fn, a->k);
+    AMP_REQUIRE(a->max_iter > 0, "%s: max_iter must be positive", fn);
+    AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES,
+                "%s: the persistent engine has no independent-trial form", fn);
+    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "%s: f32 GEMMs only (gemm %d)", fn, a->gemm);
+    const TVampWs w = tvamp_carve(d, a->k, E, a->ws, G);
+    AMP_REQUIRE(a->ws_bytes >= w.bytes, "%s: workspace %zu < %zu bytes", fn, a->ws_bytes, w.bytes);
     TrialsDecide td{};
     if (dec && (rc = trials_decide_args(d, dec, a->r, a->xmmse, td))) return rc;
     VampK P{};
     vamp_geometry(d, a->k, P);
     P.B = E;            // rows; every per-trial quantity is formed over one row (tvamp_r: Bmean = 1)
-    P.Bmean = 1;
-    P.max_iter = a->max_iter;
-    P.noise_var = a->noise_var;
-    P.sparsity = a->sparsity;
-    P.Wt0 = w.Wt0; P.Wt1 = w.Wt1; P.Wt2 = w.Wt2;
-    P.s = (const float*)a->s; P.s2 = w.s2; P.ytil = w.ytil; P.w = w.w;
-    P.r = (float*)a->r; P.xm = (float*)a->xmmse;
-    P.var0 = (float*)a->var; P.var1 = w.var1;
-    P.secmax = w.secmax; P.secabs = w.secabs; P.parts = w.parts; P.iters = w.iters;
-    P.status = (amp_status*)a->status;
-    P.y = (const float*)a->y;
-    P.x3 = 0;           // amp_status.gemm = AMP_ARITH_F32
-    P.c = to_const(c);
-    const Const64 c64 = to_const64(c);
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = tvamp_attrs())) return rc;
-    if ((rc = vamp_pack_f32(P, a, st))) return rc;   // the operators, packed once per call
-    const int g = (int)std::min<size_t>(((size_t)E * P.N + 255) / 256, 2048);
-    hipLaunchKernelGGL(tvamp_init_kernel, dim3(g), dim3(256), 0, st, P, w.nstop);
-    AMP_LAUNCH_CHECK("tvamp_init");
-    rc = gemm_store((const float*)a->y, 2 * P.n, E, 2 * P.n, P.Wt0, P.kap0, P.ncp0, P.ytil, 2 * P.k, 2 * P.k, st);
-    if (rc) return rc;
-    const dim3 g1(cdiv(E, GBM), P.ncp1 / 128);
-    for (int t = 0; t < P.max_iter; ++t) {
-        hipLaunchKernelGGL(tvamp_k1, g1, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, (const unsigned*)w.nstop);
-        AMP_LAUNCH_CHECK("tvamp_k1");
-        vamp_k2_launch<TVampK2>(P, st, t, (const unsigned*)w.nstop);
-        AMP_LAUNCH_CHECK("tvamp_k2");
-        hipLaunchKernelGGL(tvamp_r, dim3(E), dim3(RWG), 0, st, P, c64, t, w.nstop);
-        AMP_LAUNCH_CHECK("tvamp_r");
-    }
-    hipLaunchKernelGGL(tvamp_output_kernel, dim3(E), dim3(256), 0, st, P);
-    AMP_LAUNCH_CHECK("tvamp_output");
-    return dec ? trials_decide_launch(d, c, td, E, w.dec, st) : AMP_OK;
-}
-
-size_t amp_vamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t k, int32_t max_iter, int32_t trials,
-                                          int32_t per_channel) {
-    if (!d || k <= 0 || max_iter <= 0 || trials <= 0 || per_channel < 1 || d->B != 1) return 0;
-    if (d->N <= 0 || d->n <= 0 || d->M <= 0 || d->N % 2 != 0 || k > d->N || k > d->n || !vamp_index_ok(d, trials))
-        return 0;
-    int per = per_channel;
-    const int G = trial_channels(trials, per);
-    if (G > WCH_MAX) return 0;
-    return tvamp_carve(d, k, trials, nullptr, G).bytes;
-}
-
-int amp_vamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
-                           const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
-    int rc = check_dims(d, c, true, true);   // any n, any k, any even N, a partial last column tile (amp_vamp_run)
-    if (rc) return rc;
-    AMP_REQUIRE(d->B == 1, "amp_vamp_trials_ch_run: dims describe ONE trial (B = %d, must be 1)", d->B);
-    AMP_REQUIRE(trials >= 1, "amp_vamp_trials_ch_run: trials = %d", trials);
-    AMP_REQUIRE(per_channel >= 1, "amp_vamp_trials_ch_run: per_channel = %d", per_channel);
-    AMP_REQUIRE(vamp_index_ok(d, trials), "amp_vamp_trials_ch_run: %d trials of max(2N, 2n) = %d columns need more "
-                "than 32-bit offsets (or more than 65535 column tiles)", trials, 2 * std::max(d->N, d->n));
-    const int E = trials;
-    int per = per_channel;
-    const int G = trial_channels(E, per);
-    AMP_REQUIRE(G <= WCH_MAX, "amp_vamp_trials_ch_run: %d channels (at most %d per call: a grid axis)", G, WCH_MAX);
-    AMP_REQUIRE(a && a->U && a->s && a->Vh && a->y && a->r && a->xmmse && a->var && a->status && a->ws,
-                "amp_vamp_trials_ch_run: null pointer argument");
-    AMP_REQUIRE(a->k > 0 && a->k <= d->N && a->k <= d->n, "amp_vamp_trials_ch_run: k = %d must be min(n, N)", a->k);
-    AMP_REQUIRE(a->max_iter > 0, "amp_vamp_trials_ch_run: max_iter must be positive");
-    AMP_REQUIRE(a->engine == AMP_ENGINE_AUTO || a->engine == AMP_ENGINE_LAUNCHES,
-                "amp_vamp_trials_ch_run: the persistent engine has no independent-trial form");
-    AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32,
-                "amp_vamp_trials_ch_run: f32 GEMMs only (gemm %d)", a->gemm);
-    const TVampWs w = tvamp_carve(d, a->k, E, a->ws, G);
-    AMP_REQUIRE(a->ws_bytes >= w.bytes, "amp_vamp_trials_ch_run: workspace %zu < %zu bytes", a->ws_bytes, w.bytes);
-    TrialsDecide td{};
-    if (dec && (rc = trials_decide_args(d, dec, a->r, a->xmmse, td))) return rc;
-    VampK P{};
-    vamp_geometry(d, a->k, P);
-    P.B = E;            // rows; every per-trial quantity is formed over one row (tvamp_r_ch: Bmean = 1)
     P.Bmean = 1;
     P.max_iter = a->max_iter;
     P.noise_var = a->noise_var;
@@ -426,28 +285,55 @@ int amp_vamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const 
     CH.wstride[0] = (size_t)P.ncp0 * P.kap0; CH.wstride[1] = (size_t)P.ncp1 * P.kap1;
     CH.wstride[2] = (size_t)P.ncp2 * P.kap2; CH.wstride[3] = tvamp_s2_stride(P.k, G);
     const Const64 c64 = to_const64(c);
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = tvamp_ch_attrs())) return rc;
+    if ((rc = tvamp_attrs())) return rc;
     if ((rc = vamp_pack_f32_ch(P, CH, a, G, st))) return rc;   // every channel's operators, once per call
     const int gi = (int)std::min<size_t>(((size_t)E * P.N + 255) / 256, 2048);
-    hipLaunchKernelGGL(tvamp_init_ch_kernel, dim3(gi), dim3(256), 0, st, P, CH, G, w.nstop);
-    AMP_LAUNCH_CHECK("tvamp_init_ch");
+    hipLaunchKernelGGL(tvamp_init_kernel, dim3(gi), dim3(256), 0, st, P, CH, G, w.nstop);
+    AMP_LAUNCH_CHECK("tvamp_init");
     rc = gemm_store_ch((const float*)a->y, 2 * P.n, E, 2 * P.n, P.Wt0, CH.wstride[0], P.kap0, P.ncp0, P.ytil, 2 * P.k,
                        2 * P.k, per, CH.tpg, G, st);
     if (rc) return rc;
-    const int gr = G * CH.tpg;                     // <= E row tiles
-    const dim3 g1(gr, P.ncp1 / 128);
+    const int gr = G * CH.tpg;                     // <= E row tiles; one channel: cdiv(E, 32)
     for (int t = 0; t < P.max_iter; ++t) {
-        hipLaunchKernelGGL(tvamp_k1_ch, g1, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, P, CH, (const unsigned*)w.nstop);
-        AMP_LAUNCH_CHECK("tvamp_k1_ch");
-        tvamp_k2_ch_launch(P, CH, gr, t, (const unsigned*)w.nstop, st);
-        AMP_LAUNCH_CHECK("tvamp_k2_ch");
-        hipLaunchKernelGGL(tvamp_r_ch, dim3(E), dim3(RWG), 0, st, P, per, c64, t, w.nstop);
-        AMP_LAUNCH_CHECK("tvamp_r_ch");
+        rc = G == 1 ? tvamp_launch_iter(P, OneChannel{}, c64, gr, t, w.nstop, st)
+                    : tvamp_launch_iter(P, CH, c64, gr, t, w.nstop, st);
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(tvamp_output_kernel, dim3(E), dim3(256), 0, st, P);
     AMP_LAUNCH_CHECK("tvamp_output");
     return dec ? trials_decide_launch(d, c, td, E, w.dec, st) : AMP_OK;
+}
+
+}  // namespace amp
+
+using namespace amp;
+
+extern "C" {
+
+size_t amp_vamp_trials_workspace_bytes(const amp_dims* d, int32_t k, int32_t max_iter, int32_t trials) {
+    if (!d || k <= 0 || max_iter <= 0 || trials <= 0 || d->B != 1) return 0;
+    return tvamp_carve(d, k, trials, nullptr).bytes;
+}
+
+int amp_vamp_trials_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
+                        const amp_trials_decide_args* dec, int32_t trials, void* stream) {
+    return tvamp_run(d, c, a, dec, trials, trials, "amp_vamp_trials_run", (hipStream_t)stream);
+}
+
+size_t amp_vamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t k, int32_t max_iter, int32_t trials,
+                                          int32_t per_channel) {
+    if (!d || k <= 0 || max_iter <= 0 || trials <= 0 || per_channel < 1 || d->B != 1) return 0;
+    if (d->N <= 0 || d->n <= 0 || d->M <= 0 || d->N % 2 != 0 || k > d->N || k > d->n || !vamp_index_ok(d, trials))
+        return 0;
+    int per = per_channel;
+    const int G = trial_channels(trials, per);
+    if (G > WCH_MAX) return 0;
+    return tvamp_carve(d, k, trials, nullptr, G).bytes;
+}
+
+int amp_vamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
+                           const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
+    return tvamp_run(d, c, a, dec, trials, per_channel, "amp_vamp_trials_ch_run", (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -51,12 +51,12 @@ __device__ __forceinline__ size_t widx(int n, int k, int kap, int packed) {
 
 // Wt[2o][2j] = Re X, Wt[2o][2j+1] = -Im X, Wt[2o+1][2j] = Im X, Wt[2o+1][2j+1] = Re X,
 // X[o][j] = rowscale[o] * op(src[o*so + j*sj]), op = conj if `conj`; zero padding up to [ncp][kap].
-// packed: WPACK32 / WPACK16 = the MFMA-packed layouts the GEMM engines stream (amp_gemm.h),
-// WPACK_NONE = row-major.
 // rowscale multiplies like the reference's `s.view(-1,1) * Uh` (f32 x c64 -> per-component products).
-__global__ void build_cweight_kernel(const float2* __restrict__ src, long so, long sj, int conj,
-                                     const float* __restrict__ rowscale, int O, int J, float* __restrict__ wt,
-                                     int kap, int ncp, int packed) {
+// idx(n, k): where element [n][k] of the expanded weight lies.
+template <class IDX>
+__device__ __forceinline__ void cweight_fill(const float2* __restrict__ src, long so, long sj, int conj,
+                                             const float* __restrict__ rowscale, int O, int J,
+                                             float* __restrict__ wt, int kap, int ncp, const IDX& idx) {
     const long total = (long)(ncp / 2) * (kap / 2);
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int o = (int)(e / (kap / 2)), j = (int)(e % (kap / 2));
@@ -71,17 +71,37 @@ __global__ void build_cweight_kernel(const float2* __restrict__ src, long so, lo
                 xi = s * xi;
             }
         }
-        wt[widx(2 * o, 2 * j, kap, packed)] = xr;
-        wt[widx(2 * o, 2 * j + 1, kap, packed)] = -xi;
-        wt[widx(2 * o + 1, 2 * j, kap, packed)] = xi;
-        wt[widx(2 * o + 1, 2 * j + 1, kap, packed)] = xr;
+        wt[idx(2 * o, 2 * j)] = xr;
+        wt[idx(2 * o, 2 * j + 1)] = -xi;
+        wt[idx(2 * o + 1, 2 * j)] = xi;
+        wt[idx(2 * o + 1, 2 * j + 1)] = xr;
     }
 }
 
+// packed: WPACK32 / WPACK16 = the MFMA-packed layouts the GEMM engines stream (amp_gemm.h),
+// WPACK_NONE = row-major.  WPACK32, the layout of every f32 tile, has its index function compiled
+// in (its adjacent elements then go out as one store); the others share the general one.
+// Channel g = blockIdx.y reads its source at src + g * sg, its row scale at rowscale + g * rs and
+// writes its operator at wt + g * dg (64-bit offsets; one channel: a grid of one row, strides unused).
+__global__ void build_cweight_kernel(const float2* __restrict__ src, size_t sg, long so, long sj, int conj,
+                                     const float* __restrict__ rowscale, size_t rs, int O, int J,
+                                     float* __restrict__ wt, size_t dg, int kap, int ncp, int packed) {
+    src += (size_t)blockIdx.y * sg;
+    wt += (size_t)blockIdx.y * dg;
+    if (rowscale) rowscale += (size_t)blockIdx.y * rs;
+    if (packed == WPACK32)
+        cweight_fill(src, so, sj, conj, rowscale, O, J, wt, kap, ncp, [kap](int n, int k) { return wpack_index(n, k, kap); });
+    else
+        cweight_fill(src, so, sj, conj, rowscale, O, J, wt, kap, ncp,
+                     [kap, packed](int n, int k) { return widx(n, k, kap, packed); });
+}
+
 // Wt[o][j] = |src[o*so + j*sj]|^2 with torch's complex abs (correctly rounded hypot) then an
-// f32 square (bamp.py:18 `H.abs()**2`).
-__global__ void build_abs2_kernel(const float2* __restrict__ src, long so, long sj, int O, int J,
-                                  float* __restrict__ wt, int kap, int ncp) {   // always packed
+// f32 square (bamp.py:18 `H.abs()**2`); the channel on blockIdx.y as in build_cweight_kernel.
+__global__ void build_abs2_kernel(const float2* __restrict__ src, size_t sg, long so, long sj, int O, int J,
+                                  float* __restrict__ wt, size_t dg, int kap, int ncp) {   // always packed
+    src += (size_t)blockIdx.y * sg;
+    wt += (size_t)blockIdx.y * dg;
     const long total = (long)ncp * kap;
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int o = (int)(e / kap), j = (int)(e % kap);
@@ -102,17 +122,24 @@ __global__ void pack_weight_kernel(const float* __restrict__ src, float* __restr
         dst[wpack_index((int)(e / kap), (int)(e % kap), kap)] = src[e];
 }
 
+// one launch of build_cweight_kernel over nch channels
+static int launch_cweight(const char* what, const float2* src, size_t sg, long so, long sj, int conj,
+                          const float* rowscale, size_t rs, int O, int J, float* wt, size_t dg, int kap, int ncp,
+                          int packed, int nch, hipStream_t st) {
+    const long total = (long)(ncp / 2) * (kap / 2);
+    const int grid = (int)std::min<long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(build_cweight_kernel, dim3(grid, nch), dim3(256), 0, st, src, sg, so, sj, conj, rowscale, rs, O,
+                       J, wt, dg, kap, ncp, packed);
+    AMP_LAUNCH_CHECK(what);
+    return AMP_OK;
+}
+
 int build_cweight(const float2* src, long so, long sj, int conj, const float* rowscale, int O, int J, float* wt,
                   int kap, int ncp, hipStream_t st, int packed) {
     AMP_REQUIRE(packed == WPACK_NONE || (kap % GBK == 0 && ncp % 128 == 0) ||
                     (packed == WPACK16 && kap % 16 == 0 && ncp % 16 == 0),
                 "build_cweight: kap %d / ncp %d not tiled", kap, ncp);
-    const long total = (long)(ncp / 2) * (kap / 2);
-    const int grid = (int)std::min<long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(build_cweight_kernel, dim3(grid), dim3(256), 0, st, src, so, sj, conj, rowscale, O, J, wt,
-                       kap, ncp, packed);
-    AMP_LAUNCH_CHECK("build_cweight");
-    return AMP_OK;
+    return launch_cweight("build_cweight", src, 0, so, sj, conj, rowscale, 0, O, J, wt, 0, kap, ncp, packed, 1, st);
 }
 
 struct CWeightJobs {
@@ -334,12 +361,7 @@ int build_cweights(const CWeightJob* jobs, int njobs, unsigned* zero, int nzero,
 
 int build_abs2_weight(const float2* src, long so, long sj, int O, int J, float* wt, int kap, int ncp,
                       hipStream_t st) {
-    AMP_REQUIRE(kap % GBK == 0 && ncp % 128 == 0, "build_abs2_weight: kap %d / ncp %d not tiled", kap, ncp);
-    const long total = (long)ncp * kap;
-    const int grid = (int)std::min<long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(build_abs2_kernel, dim3(grid), dim3(256), 0, st, src, so, sj, O, J, wt, kap, ncp);
-    AMP_LAUNCH_CHECK("build_abs2_weight");
-    return AMP_OK;
+    return build_abs2_weight_ch(src, 0, so, sj, O, J, wt, 0, kap, ncp, 1, st);
 }
 
 template <int BN>
@@ -356,20 +378,25 @@ template int set_lds_attr<128>(const void*);
 template int set_lds_attr<256>(const void*);
 
 // Plain GEMM: C[rows][ldc] = A[rows][lda](ka valid) . Wt^T, columns [0, nc) stored.  AL: A's loader
-// (ALoadPair where its rows are only 8-byte aligned: VAMP's y at odd n)
+// (ALoadPair where its rows are only 8-byte aligned: VAMP's y at odd n).  The row tile's channel
+// (amp_trials.h TrialChannels::tile; one channel: per = rows): the channel's operator at
+// wt + g * dg, its rows up to the channel's limit staged (the next channel's as zeros) and stored.
 template <int BN, class AL = ALoadPlain>
 __global__ __launch_bounds__(AMP_WG) void gemm_store_kernel(const float* __restrict__ a, int lda, int rows, int ka,
-                                                            const float* __restrict__ wt, int kap,
-                                                            float* __restrict__ c, int ldc, int nc) {
+                                                            const float* __restrict__ wt, size_t dg, int kap,
+                                                            float* __restrict__ c, int ldc, int nc, int per, int tpg) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const GemmTile tile = xcd_tile();
-    const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    gemm_tile<BN>(AL{a, lda, rows, ka}, wt, kap, row0, col0, lds);
+    TrialChannels CH{};
+    CH.per = per; CH.tpg = tpg;
+    const ChannelTile ct = CH.tile(tile.rb, rows);
+    const int row0 = ct.row0, col0 = tile.cb * BN;
+    gemm_tile<BN>(AL{a, lda, ct.lim, ka}, wt + (size_t)ct.g * dg, kap, row0, col0, lds);
     using C = GemmCfg<BN>;
     for (int e = threadIdx.x; e < GBM * BN; e += AMP_WG) {
         const int rho = e / BN, cc = e % BN;
         const int row = row0 + rho, col = col0 + cc;
-        if (row < rows && col < nc) c[(size_t)row * ldc + col] = lds[rho * C::LDC + cc];
+        if (row < ct.lim && col < nc) c[(size_t)row * ldc + col] = lds[rho * C::LDC + cc];
     }
 }
 
@@ -384,9 +411,12 @@ __global__ __launch_bounds__(256) void weight_kband_init(int* __restrict__ band,
     if (t < ntiles) { band[2 * t] = G; band[2 * t + 1] = -1; }
 }
 
-__global__ __launch_bounds__(256) void weight_kband_kernel(const float4* __restrict__ wp, int G, int cgs, int gps,
-                                                           int* __restrict__ band) {
+// The channel on blockIdx.z: its operator at wp + z * dg4 float4s, its ranges at band + z * bstride.
+__global__ __launch_bounds__(256) void weight_kband_kernel(const float4* __restrict__ wp, size_t dg4, int G, int cgs,
+                                                           int gps, int* __restrict__ band, int bstride) {
     __shared__ int s_lo, s_hi;
+    wp += (size_t)blockIdx.z * dg4;
+    band += (size_t)blockIdx.z * bstride;
     if (threadIdx.x == 0) { s_lo = G; s_hi = -1; }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -418,106 +448,20 @@ __global__ __launch_bounds__(256) void weight_kband_fin(int* __restrict__ band, 
 }
 
 int weight_kband(const float* wp, int kap, int ncp, int BN, int* band, hipStream_t st) {
-    AMP_REQUIRE(kap % GBK == 0 && ncp % BN == 0 && BN % 32 == 0, "weight_kband: kap %d / ncp %d / BN %d", kap, ncp,
-                BN);
-    const int nt = ncp / BN, G = kap / 8;
-    const int gps = 64;                                    // reduction groups per slice: 64 KB per tile-slice
-    hipLaunchKernelGGL(weight_kband_init, dim3(cdiv(nt, 256)), dim3(256), 0, st, band, nt, G);
-    hipLaunchKernelGGL(weight_kband_kernel, dim3(nt, cdiv(G, gps)), dim3(256), 0, st, (const float4*)wp, G, BN / 32,
-                       gps, band);
-    hipLaunchKernelGGL(weight_kband_fin, dim3(cdiv(nt, 256)), dim3(256), 0, st, band, nt);
-    AMP_LAUNCH_CHECK("weight_kband");
-    return AMP_OK;
+    AMP_REQUIRE(BN > 0 && ncp % BN == 0, "weight_kband: ncp %d / BN %d", ncp, BN);
+    return weight_kband_ch(wp, 0, kap, ncp, BN, band, 2 * (ncp / BN), 1, st);
 }
 
-// ---- the same three builders for G channels in one launch each (amp_bamp_trials_ch_run /
-// amp_scamp_trials_ch_run): channel g = blockIdx.y (blockIdx.z for the band scan) reads its source at
-// src + g * sg and writes its MFMA-packed operator at wt + g * dg (64-bit offsets) and its band ranges
-// at band + g * bstride.  Every value is formed as in the single-channel kernels above: a channel's
-// operator and ranges have the bits a call of build_cweight / build_abs2_weight / weight_kband on that
-// channel alone gives. ----
-
-__global__ void build_cweight_ch_kernel(const float2* __restrict__ src, size_t sg, long so, long sj, int conj, int O,
-                                        int J, float* __restrict__ wt, size_t dg, int kap, int ncp,
-                                        const float* __restrict__ rowscale, size_t rs) {
-    src += (size_t)blockIdx.y * sg;
-    wt += (size_t)blockIdx.y * dg;
-    if (rowscale) rowscale += (size_t)blockIdx.y * rs;
-    const long total = (long)(ncp / 2) * (kap / 2);
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int o = (int)(e / (kap / 2)), j = (int)(e % (kap / 2));
-        float xr = 0.f, xi = 0.f;
-        if (o < O && j < J) {
-            const float2 v = src[o * so + j * sj];
-            xr = v.x;
-            xi = conj ? -v.y : v.y;
-            if (rowscale) {
-                const float s = rowscale[o];
-                xr = s * xr;
-                xi = s * xi;
-            }
-        }
-        wt[wpack_index(2 * o, 2 * j, kap)] = xr;
-        wt[wpack_index(2 * o, 2 * j + 1, kap)] = -xi;
-        wt[wpack_index(2 * o + 1, 2 * j, kap)] = xi;
-        wt[wpack_index(2 * o + 1, 2 * j + 1, kap)] = xr;
-    }
-}
-
-__global__ void build_abs2_ch_kernel(const float2* __restrict__ src, size_t sg, long so, long sj, int O, int J,
-                                     float* __restrict__ wt, size_t dg, int kap, int ncp) {
-    src += (size_t)blockIdx.y * sg;
-    wt += (size_t)blockIdx.y * dg;
-    const long total = (long)ncp * kap;
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int o = (int)(e / kap), j = (int)(e % kap);
-        float v = 0.f;
-        if (o < O && j < J) {
-            const float2 z = src[o * so + j * sj];
-            const float a = (float)sqrt((double)z.x * z.x + (double)z.y * z.y);
-            v = a * a;
-        }
-        wt[wpack_index(o, j, kap)] = v;
-    }
-}
-
-// weight_kband_kernel with the channel on blockIdx.z
-__global__ __launch_bounds__(256) void weight_kband_ch_kernel(const float4* __restrict__ wp, size_t dg4, int G, int cgs,
-                                                              int gps, int* __restrict__ band, int bstride) {
-    __shared__ int s_lo, s_hi;
-    wp += (size_t)blockIdx.z * dg4;
-    band += (size_t)blockIdx.z * bstride;
-    if (threadIdx.x == 0) { s_lo = G; s_hi = -1; }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int cg0 = blockIdx.x * cgs;
-    const int ga = blockIdx.y * gps, gn = min(gps, G - ga);
-    int lo = G, hi = -1;
-    for (int b = wave; b < cgs * gn; b += blockDim.x >> 6) {   // wave-uniform
-        const int cg = cg0 + b / gn, g = ga + b % gn;
-        const float4 v = wp[((size_t)cg * G + g) * 64 + lane];
-        const bool nz = (v.x != 0.f) | (v.y != 0.f) | (v.z != 0.f) | (v.w != 0.f) | (v.x != v.x) | (v.y != v.y) |
-                        (v.z != v.z) | (v.w != v.w);
-        if (__any(nz)) { lo = min(lo, g); hi = max(hi, g); }
-    }
-    if (lane == 0) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_hi >= 0) {
-        atomicMin(&band[2 * blockIdx.x], s_lo);
-        atomicMax(&band[2 * blockIdx.x + 1], s_hi);
-    }
-}
+// ---- the builders for nch channels in one launch each (the trial engines; the single-channel
+// functions above are their nch = 1 case): channel g reads its source at src + g * sg and writes its
+// MFMA-packed operator at wt + g * dg and its band ranges at band + g * bstride. ----
 
 int build_cweight_ch(const float2* src, size_t sg, long so, long sj, int conj, int O, int J, float* wt, size_t dg,
                      int kap, int ncp, int nch, hipStream_t st, const float* rowscale, size_t rs) {
     AMP_REQUIRE(kap % GBK == 0 && ncp % 128 == 0 && nch >= 1 && nch <= WCH_MAX,
                 "build_cweight_ch: kap %d / ncp %d not tiled, or %d channels", kap, ncp, nch);
-    const long total = (long)(ncp / 2) * (kap / 2);
-    const int grid = (int)std::min<long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(build_cweight_ch_kernel, dim3(grid, nch), dim3(256), 0, st, src, sg, so, sj, conj, O, J, wt, dg,
-                       kap, ncp, rowscale, rs);
-    AMP_LAUNCH_CHECK("build_cweight_ch");
-    return AMP_OK;
+    return launch_cweight("build_cweight_ch", src, sg, so, sj, conj, rowscale, rs, O, J, wt, dg, kap, ncp, WPACK32, nch,
+                          st);
 }
 
 int build_abs2_weight_ch(const float2* src, size_t sg, long so, long sj, int O, int J, float* wt, size_t dg, int kap,
@@ -526,7 +470,7 @@ int build_abs2_weight_ch(const float2* src, size_t sg, long so, long sj, int O, 
                 "build_abs2_weight_ch: kap %d / ncp %d not tiled, or %d channels", kap, ncp, nch);
     const long total = (long)ncp * kap;
     const int grid = (int)std::min<long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(build_abs2_ch_kernel, dim3(grid, nch), dim3(256), 0, st, src, sg, so, sj, O, J, wt, dg, kap, ncp);
+    hipLaunchKernelGGL(build_abs2_kernel, dim3(grid, nch), dim3(256), 0, st, src, sg, so, sj, O, J, wt, dg, kap, ncp);
     AMP_LAUNCH_CHECK("build_abs2_weight_ch");
     return AMP_OK;
 }
@@ -543,7 +487,7 @@ int weight_kband_ch(const float* wp, size_t dg, int kap, int ncp, int BN, int* b
     AMP_REQUIRE(slots <= 0x7fffffffL, "weight_kband_ch: %ld band slots", slots);
     const int gps = 64;
     hipLaunchKernelGGL(weight_kband_init, dim3(cdiv((int)slots, 256)), dim3(256), 0, st, band, (int)slots, G);
-    hipLaunchKernelGGL(weight_kband_ch_kernel, dim3(nt, cdiv(G, gps), nch), dim3(256), 0, st, (const float4*)wp, dg / 4,
+    hipLaunchKernelGGL(weight_kband_kernel, dim3(nt, cdiv(G, gps), nch), dim3(256), 0, st, (const float4*)wp, dg / 4,
                        G, BN / 32, gps, band, bstride);
     hipLaunchKernelGGL(weight_kband_fin, dim3(cdiv((int)slots, 256)), dim3(256), 0, st, band, (int)slots);
     AMP_LAUNCH_CHECK("weight_kband_ch");
@@ -594,6 +538,11 @@ int fix_grid(int nblk, int work) {
 
 int gemm_store(const float* a, int lda, int rows, int ka, const float* wt, int kap, int ncp, float* c, int ldc,
                int nc, hipStream_t st) {
+    return gemm_store_ch(a, lda, rows, ka, wt, 0, kap, ncp, c, ldc, nc, rows, cdiv(rows, GBM), 1, st);
+}
+
+int gemm_store_ch(const float* a, int lda, int rows, int ka, const float* wt, size_t dg, int kap, int ncp, float* c,
+                  int ldc, int nc, int per, int tpg, int nch, hipStream_t st) {
     static bool attr = false;
     if (!attr) {
         int rc = set_lds_attr<128>((const void*)gemm_store_kernel<128>);
@@ -601,62 +550,18 @@ int gemm_store(const float* a, int lda, int rows, int ka, const float* wt, int k
         if (rc) return rc;
         attr = true;
     }
-    dim3 grid(cdiv(rows, GBM), ncp / 128);
-    // rows of lda % 4 == 2 floats (or ka % 4 == 2 valid ones): the pair loader, the same staged values
-    AMP_REQUIRE(lda % 2 == 0 && ka % 2 == 0 && ka >= 2, "gemm_store: lda %d / ka %d must be even", lda, ka);
-    if (lda % 4 != 0 || ka % 4 != 0) {
-        hipLaunchKernelGGL((gemm_store_kernel<128, ALoadPair>), grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a, lda,
-                           rows, ka, wt, kap, c, ldc, nc);
-        AMP_LAUNCH_CHECK("gemm_store");
-        return AMP_OK;
-    }
-    hipLaunchKernelGGL(gemm_store_kernel<128>, grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a, lda, rows, ka, wt,
-                       kap, c, ldc, nc);
-    AMP_LAUNCH_CHECK("gemm_store");
-    return AMP_OK;
-}
-
-// gemm_store_kernel with the row tile's channel (amp_trials.h channel_tile): the channel's operator,
-// its rows up to the channel's limit staged (the next channel's as zeros) and stored
-template <int BN, class AL = ALoadPlain>
-__global__ __launch_bounds__(AMP_WG) void gemm_store_ch_kernel(const float* __restrict__ a, int lda, int rows, int ka,
-                                                               const float* __restrict__ wt, size_t dg, int kap,
-                                                               float* __restrict__ c, int ldc, int nc, int per, int tpg) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const GemmTile tile = xcd_tile();
-    TrialChannels CH{};
-    CH.per = per; CH.tpg = tpg;
-    const ChannelTile ct = channel_tile(CH, tile.rb, rows);
-    const int row0 = ct.row0, col0 = tile.cb * BN;
-    gemm_tile<BN>(AL{a, lda, ct.lim, ka}, wt + (size_t)ct.g * dg, kap, row0, col0, lds);
-    using C = GemmCfg<BN>;
-    for (int e = threadIdx.x; e < GBM * BN; e += AMP_WG) {
-        const int rho = e / BN, cc = e % BN;
-        const int row = row0 + rho, col = col0 + cc;
-        if (row < ct.lim && col < nc) c[(size_t)row * ldc + col] = lds[rho * C::LDC + cc];
-    }
-}
-
-int gemm_store_ch(const float* a, int lda, int rows, int ka, const float* wt, size_t dg, int kap, int ncp, float* c,
-                  int ldc, int nc, int per, int tpg, int nch, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        int rc = set_lds_attr<128>((const void*)gemm_store_ch_kernel<128>);
-        if (!rc) rc = set_lds_attr<128>((const void*)gemm_store_ch_kernel<128, ALoadPair>);
-        if (rc) return rc;
-        attr = true;
-    }
     AMP_REQUIRE(lda % 2 == 0 && ka % 2 == 0 && ka >= 2, "gemm_store_ch: lda %d / ka %d must be even", lda, ka);
     AMP_REQUIRE(per >= 1 && tpg == cdiv(per, GBM) && nch == cdiv(rows, per) && nch <= WCH_MAX,
                 "gemm_store_ch: %d rows at %d per channel, %d tiles per channel, %d channels", rows, per, tpg, nch);
     dim3 grid(nch * tpg, ncp / 128);
-    // as gemm_store: the pair loader where rows are only 8-byte aligned (a channel's first row may be odd;
-    // lda is even, so every row stays 8-byte aligned, and 16-byte aligned where lda % 4 == 0)
+    // rows of lda % 4 == 2 floats (or ka % 4 == 2 valid ones): the pair loader, the same staged values (a
+    // channel's first row may be odd; lda is even, so every row stays 8-byte aligned, and 16-byte aligned
+    // where lda % 4 == 0)
     if (lda % 4 != 0 || ka % 4 != 0)
-        hipLaunchKernelGGL((gemm_store_ch_kernel<128, ALoadPair>), grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a,
+        hipLaunchKernelGGL((gemm_store_kernel<128, ALoadPair>), grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a,
                            lda, rows, ka, wt, dg, kap, c, ldc, nc, per, tpg);
     else
-        hipLaunchKernelGGL(gemm_store_ch_kernel<128>, grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a, lda, rows, ka,
+        hipLaunchKernelGGL(gemm_store_kernel<128>, grid, dim3(AMP_WG), GemmCfg<128>::LDS_BYTES, st, a, lda, rows, ka,
                            wt, dg, kap, c, ldc, nc, per, tpg);
     AMP_LAUNCH_CHECK("gemm_store_ch");
     return AMP_OK;

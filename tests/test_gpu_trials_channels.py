@@ -119,7 +119,7 @@ def _state(name):
     return 'psi' if tc.algo_of(name) == 'scamp' else 'var'
 
 
-@pytest.mark.parametrize('nE,R', [(40, 1), (40, 5), (40, 32), (40, 33), (1, 1)])
+@pytest.mark.parametrize('nE,R', [(40, 1), (40, 5), (40, 32), (40, 33), (40, 40), (1, 1)])
 @pytest.mark.parametrize('name', tc.POINT_IDS)
 def test_trials_channels_equal_sequential_forwards(device, name, nE, R):
     recs, xmap, xm, st = grouped(name, nE, R)

@@ -112,7 +112,7 @@ def _differences(rec, bufs, ref):
     return d
 
 
-@pytest.mark.parametrize('nE,R', [(40, 1), (40, 5), (40, 32), (40, 33), (1, 1)])
+@pytest.mark.parametrize('nE,R', [(40, 1), (40, 5), (40, 32), (40, 33), (40, 40), (1, 1)])
 @pytest.mark.parametrize('name', vc.POINT_IDS)
 def test_vamp_trials_channels_equal_sequential_forwards(device, name, nE, R):
     recs, r, xm, var = grouped(name, nE, R)
