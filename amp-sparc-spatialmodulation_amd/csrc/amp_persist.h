@@ -1021,16 +1021,46 @@ __device__ __forceinline__ void part_publish_keys(PartAcc p, __amdgpu_buffer_rsr
 // 0.0 + g0 + g1 + g2 + g3 over lane + 64 q); one wave-uniform test over every lane's words sends a
 // sweep that holds a NaN through part_gather's fold and part_wave_reduce.  The tree is
 // part_wave_reduce_keys' (its NaN test has been made: the keys go in directly).
+// POLL >= 1: the retry loop with no memory round trip of its own between two sweeps.  The abort word's
+// load and the clock read are issued ahead of the sweep's loads (they return with them) and are
+// looked at behind the tag test, so a sweep that finds a granule untagged goes to the next one after
+// the s_sleep alone; a word found raised still ends the gather with that sweep, and the 2 s bound
+// still raises it.  POLL >= 2: a sweep's loads are issued together, not pair by pair (below).
+// Granules, tags, the loads' addresses and scope, the folds and both barriers are the other form's.
+// nsweeps (wave 0): the sweeps this gather took (the phase trace's count).
+template <int POLL = 0>
 __device__ __forceinline__ bool part_gather_keys(__amdgpu_buffer_rsrc_t rs, unsigned off0, int nwg, unsigned tag,
-                                                 unsigned* abort_word, PartAcc& out, void* lds_scratch, int* s_flag) {
+                                                 unsigned* abort_word, PartAcc& out, void* lds_scratch, int* s_flag,
+                                                 unsigned* nsweeps = nullptr) {
     Partial* s = reinterpret_cast<Partial*>(lds_scratch);
     if ((threadIdx.x >> 6) == 0) {
         const int lane = threadIdx.x & 63;
         u32x4 a[4], b[4];
         int ok_all = 1;
+        unsigned nsw = 0;
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
         for (;;) {
+            unsigned raised = 0u;
+            uint64_t now = t0;
+            if constexpr (POLL >= 1) {
+                raised = __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                now = __builtin_amdgcn_s_memrealtime();
+            }
             bool ok = true;
+            if constexpr (POLL >= 2) {
+                // all eight loads of a sweep in flight at once: behind a lane-divergent branch each pair
+                // was waited for before the next was issued (up to four round trips per sweep).  A
+                // lane past nwg loads too, at the address the formula gives it (a later iteration's
+                // granule, or past the resource's end: zeros); its words are never looked at.
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int w = lane + 64 * q;
+                    a[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off0 + 32u * w), 0, 16);
+                    b[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off0 + 32u * w + 16), 0, 16);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) ok &= !(lane + 64 * q < nwg) | ((a[q].w == tag) & (b[q].w == tag));
+            } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int w = lane + 64 * q;
@@ -1040,15 +1070,21 @@ __device__ __forceinline__ bool part_gather_keys(__amdgpu_buffer_rsrc_t rs, unsi
                     ok &= (a[q].w == tag) & (b[q].w == tag);
                 }
             }
+            }
+            ++nsw;
             if (__all(ok)) break;
-            if (__hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-                __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {   // 2 s at 100 MHz
+            if constexpr (POLL == 0) {
+                raised = __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (raised == 0u) now = __builtin_amdgcn_s_memrealtime();
+            }
+            if (raised != 0u || now - t0 > 200000000ull) {   // 2 s at 100 MHz
                 __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 ok_all = 0;
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
         }
+        if (nsweeps) *nsweeps = nsw;
         PartAcc p;
         bool isnan_ = false;
 #pragma unroll

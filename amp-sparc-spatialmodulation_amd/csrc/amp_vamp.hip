@@ -539,7 +539,10 @@ int amp_vamp_run_sharded(const amp_dims* d, const amp_constellation* c, const am
 // boundary: trace[(wg * max_iter + t) * 10 + phase], phases = start, r~ built, GEMM1, w stored,
 // GEMM2 + r, partial published, barrier passed, scalars ready, denoiser done, vamp_advance started; then per
 // workgroup [nwg * max_iter * 10 + 2 * wg] = s_memtime / s_memrealtime at kernel start and
-// [nwg * max_iter * 10 + 2 * nwg + 2 * wg] the same pair at its end (trace: 4 nwg more words).
+// [nwg * max_iter * 10 + 2 * nwg + 2 * wg] the same pair at its end (trace: 4 nwg more words), and
+// behind them nwg * max_iter words [wg * max_iter + t]: the sweeps the gather of iteration t took
+// (the eight-wave bf16x3 kernels write them; the others leave them as the caller set them).  The
+// ten-slot stride stays, so that the other kernels' stamp addresses, and code, stay what they were.
 int amp_vamp_persist_trace_reuse(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* trace,
                                  int32_t reuse, void* stream) {
     VampK P;

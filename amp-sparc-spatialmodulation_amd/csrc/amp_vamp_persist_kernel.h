@@ -48,6 +48,9 @@ constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iter
 #ifndef AMP_X3_W8_XCH
 #define AMP_X3_W8_XCH 1                 // the eight-wave form's exchange reduces its extremes on integer keys (A/B builds: 0)
 #endif
+#ifndef AMP_X3_W8_POLL
+#define AMP_X3_W8_POLL 2                // the eight-wave form's gather: 1 retries without a dependent abort-word load, 2 also
+#endif                                  // issues a sweep's loads together (A/B builds: 0, 1)
 #ifndef AMP_SCALAR_TAIL
 #define AMP_SCALAR_TAIL 1               // bf16x3 at one workgroup per CU: the LMMSE scalars of vamp_advance inside the
 #endif                                  // next iteration's GEMM1, behind group 0 (A/B builds: 0, the unsplit form)
@@ -163,6 +166,10 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // integer keys and the mean's quotient by a power of two as a scaling (amp_persist.h
     // part_publish_keys / part_gather_keys, amp_vamp.h vamp_advance_head_pow2); same bits
     constexpr bool XCH = X3PF && NWV == 8 && OCC == 1 && AMP_X3_W8_XCH;
+    // the same kernels: the gather's retry loop with the abort word's load and the clock read issued
+    // with each sweep instead of behind a failed one, and a sweep's eight loads in flight together
+    // (amp_persist.h part_gather_keys POLL)
+    constexpr int POLL = XCH ? AMP_X3_W8_POLL : 0;
     constexpr int CN = 8 * NT * NWV;
     constexpr AopLayout CY = aop_layout(CN);
 #define c64 (static_cast<const Const64&>(*Dp))
@@ -371,7 +378,10 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
             if constexpr (STAIL == 0) s2x = s2_lane(P, P.s + (size_t)ep * P.sch);
             const unsigned tag = P.gen * (unsigned)(P.max_iter + 1) + (unsigned)te + 1u;
             if constexpr (XCH) {
-                if (!part_gather_keys(grs, ((unsigned)te * nwx + wg0) * 32u, P.wpe, tag, P.pbar + 1, g, scr, &s_flag)) return false;
+                unsigned nsw = 0;
+                if (!part_gather_keys<POLL>(grs, ((unsigned)te * nwx + wg0) * 32u, P.wpe, tag, P.pbar + 1, g, scr, &s_flag, &nsw)) return false;
+                // the trace's sweep counts: one word per (workgroup, iteration) behind the end stamps
+                if (trc && tid == 0 && te < P.max_iter) trc[(size_t)nwg * P.max_iter * AMP_TRACE_STRIDE + 4 * nwg + (size_t)wg * P.max_iter + te] = nsw;
             } else {
                 if (!part_gather(grs, ((unsigned)te * nwx + wg0) * 32u, P.wpe, tag, P.pbar + 1, g, scr, &s_flag)) return false;
             }
@@ -626,6 +636,7 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 // the tail of the record that drives this iteration (t >= 1; iteration 0's is whole:
                 // vamp_first_iter), complete before the w epilogue reads cur.vr: behind group 0's MFMAs
                 // and the request of group 1's operators
+                // (behind group 1 in the SIMD's second wave, waves 4-7, it measured slower: DESIGN.md §3.1)
                 auto tail0 = [&](int g) __attribute__((always_inline)) {
                     if (g == 0 && t > 0) {
                         S2Lane s2x;

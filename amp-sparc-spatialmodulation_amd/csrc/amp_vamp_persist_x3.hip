@@ -407,7 +407,7 @@ __global__ __launch_bounds__(XRD_WG) void exchange_reduce_debug_kernel(const Par
     for (int form = 0; form < 2; ++form) {
         PartAcc g;
         const bool ok = form == 0 ? part_gather(srs, 0u, ngran, tag, out + XRD_FLAGS / 4, g, scr, &s_flag)
-                                  : part_gather_keys(srs, 0u, ngran, tag, out + XRD_FLAGS / 4, g, scr, &s_flag);
+                                  : part_gather_keys<AMP_X3_W8_POLL>(srs, 0u, ngran, tag, out + XRD_FLAGS / 4, g, scr, &s_flag);
         if (tid == 0) {
             Partial o;
             o.sumvar = g.sumvar; o.maxabs = g.maxabs; o.minsecmax = g.minsecmax; o.notclose = g.notclose;
@@ -430,5 +430,59 @@ int amp_exchange_reduce_debug(const void* vals, const void* grans, int32_t ngran
     hipLaunchKernelGGL(exchange_reduce_debug_kernel, dim3(1), dim3(XRD_WG), 0, (hipStream_t)stream, (const Partial*)vals,
                        (const u32x4*)grans, (int)ngran, (const double*)sums, (const int2*)divs, (unsigned*)out);
     AMP_LAUNCH_CHECK("amp_exchange_reduce_debug");
+    return AMP_OK;
+}
+
+// Diagnostic (amp_exchange_poll_debug): the gather of the eight-wave bf16x3 kernel's exchange as the
+// kernel calls it (part_gather_keys with the kernel's retry loop), one workgroup of eight waves on
+// caller-supplied granule pairs whose tag words are the caller's, with the abort word preset.  A
+// call that would wait (a tag absent and the word not raised) is not run: the kernel looks at the
+// tags first and leaves code 2.
+namespace amp {
+
+constexpr unsigned XPL_REC = 0, XPL_ABORT = 32, XPL_SWEEPS = 36, XPL_CODE = 40, XPL_TICKS = 48;   // (out: 64 bytes)
+
+__global__ __launch_bounds__(XRD_WG) void exchange_poll_debug_kernel(const u32x4* grans, int ngran, unsigned tag,
+                                                                      unsigned raised, unsigned* out) {
+    __shared__ __attribute__((aligned(16))) unsigned scr[256];
+    __shared__ int s_flag;
+    const int tid = threadIdx.x;
+    int present = 1;
+    if (tid < ngran) present = (grans[2 * tid].w == tag) & (grans[2 * tid + 1].w == tag);
+    const int all = __syncthreads_and(present);
+    if (tid == 0) {
+        out[XPL_ABORT / 4] = raised;
+        out[XPL_SWEEPS / 4] = 0u;
+        out[XPL_CODE / 4] = (all || raised != 0u) ? 0u : 2u;
+    }
+    if (!all && raised == 0u) return;
+    __threadfence();
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t srs = gran_rsrc(const_cast<u32x4*>(grans), (unsigned)ngran * 32u);
+    PartAcc g;
+    unsigned nsw = 0;
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    const bool ok = part_gather_keys<AMP_X3_W8_POLL>(srs, 0u, ngran, tag, out + XPL_ABORT / 4, g, scr, &s_flag, &nsw);
+    const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
+    if (tid == 0) {
+        Partial o;
+        o.sumvar = g.sumvar; o.maxabs = g.maxabs; o.minsecmax = g.minsecmax; o.notclose = g.notclose;
+        o.pad = ok ? 1u : 0u;
+        *reinterpret_cast<Partial*>(reinterpret_cast<char*>(out) + XPL_REC) = o;
+        out[XPL_SWEEPS / 4] = nsw;
+        *reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(out) + XPL_TICKS) = t1 - t0;
+    }
+}
+
+}  // namespace amp
+
+int amp_exchange_poll_debug(const void* grans, int32_t ngran, uint32_t tag, int32_t raised, void* out, void* stream) {
+    using namespace amp;
+    AMP_REQUIRE(grans && out, "amp_exchange_poll_debug: null pointer argument");
+    AMP_REQUIRE(ngran >= 1 && ngran <= XRD_MAXG, "amp_exchange_poll_debug: ngran = %d (1 ... %d)", ngran, XRD_MAXG);
+    AMP_REQUIRE(tag != 0u, "amp_exchange_poll_debug: tag 0 (never published)");
+    hipLaunchKernelGGL(exchange_poll_debug_kernel, dim3(1), dim3(XRD_WG), 0, (hipStream_t)stream, (const u32x4*)grans,
+                       (int)ngran, (unsigned)tag, raised != 0 ? 1u : 0u, (unsigned*)out);
+    AMP_LAUNCH_CHECK("amp_exchange_poll_debug");
     return AMP_OK;
 }

@@ -159,7 +159,9 @@ int amp_vamp_select_gemm(const amp_dims* d, int32_t k, int32_t gemm);
  * amp_vamp_select_gemm is K = 0: at most 16 points. */
 int amp_vamp_select_gemm_k(const amp_dims* d, int32_t k, int32_t gemm, int32_t K);
 /* Diagnostic: a persistent-engine forward that stamps s_memtime per workgroup, iteration and
- * phase into trace (device, nwg * max_iter * 10 + 4 * nwg uint64; layout in amp_vamp.hip). */
+ * phase into trace (device, nwg * max_iter * 11 + 4 * nwg uint64: ten stamps per workgroup and
+ * iteration, 4 nwg start / end clock words, then nwg * max_iter gather sweep counts; layout in
+ * amp_vamp.hip). */
 int amp_vamp_persist_trace(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a, void* trace,
                            void* stream);
 /* Diagnostic (bench.py): while on != 0, every persistent VAMP launch records a HIP event pair
@@ -517,6 +519,15 @@ int amp_x3_planes_debug(const void* rows, int32_t nrows, void* planes, void* str
  *          quotients of the division, at 4768 of the scaling form; from 8864 on scratch. */
 int amp_exchange_reduce_debug(const void* vals, const void* grans, int32_t ngran, const void* sums, const void* divs,
                               void* out, void* stream);
+/* Diagnostic: the gather of the eight-wave bf16x3 kernel's exchange with the kernel's retry loop, in
+ * one workgroup of eight waves, on granule pairs whose tag words are the caller's.
+ *   grans  [ngran][8] uint32, 1 <= ngran <= 256 (the layout above; words 3 and 7 are the tags);
+ *   tag    the tag swept for (not 0); raised: the abort word's value before the gather (0 or 1);
+ *   out    64 bytes: at 0 the gathered record (the vals layout, last word 1: every tag was found,
+ *          0: the gather gave up), at 32 the abort word after the gather, at 36 the sweeps it took,
+ *          at 40 a code (0: the gather ran; 2: a tag is absent and the word is not raised, so the
+ *          gather would wait and was not run), at 48 uint64 the gather's duration in 10 ns ticks. */
+int amp_exchange_poll_debug(const void* grans, int32_t ngran, uint32_t tag, int32_t raised, void* out, void* stream);
 /* Same counters with Loss.random_decision (loss.py:252-280, generator_mode='random'): per
  * channel use the Na largest |x_m| (NaN largest; exact ties by larger index), each decided to
  * its nearest point, compared in ascending position order with the row's true sorted indices.

@@ -102,7 +102,8 @@ def main():
         det.detect(inp['U'], inp['s'], inp['Vh'], inp['y'], inp['SNR'])
     T = det.detect(inp['U'], inp['s'], inp['Vh'], inp['y'], inp['SNR'])
     nwg = (B + 15) // 16
-    tr = torch.zeros(nwg * iters * STRIDE + 4 * nwg, dtype=torch.int64, device=dev)
+    # ten stamps per (workgroup, iteration), 4 nwg start / end clock words, then the gathers' sweep counts
+    tr = torch.zeros(nwg * iters * STRIDE + 4 * nwg + nwg * iters, dtype=torch.int64, device=dev)
     s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s0.record()
     b0 = nat.prepare_counts()
@@ -138,7 +139,20 @@ def main():
     elif Tn > 1 and np.all(raw[:, :, 9] > 0):   # slot 9: the start of vamp_advance (the scalars' own work)
         print(f'  scalars: gather end -> advance start median {np.median(raw[:, :, 9] - raw[:, :, 6]):.0f}, '
               f'vamp_advance median {np.median(raw[:, :, 7] - raw[:, :, 9]):.0f} cycles')
+    sweep_counts(a, nwg, iters, Tn)
     arrival_spread(a, st, nwg, iters, Tn)
+
+
+def sweep_counts(a, nwg, iters, Tn):
+    """Sweeps per gather (the words behind the clock pairs, [wg, t]): written by the eight-wave bf16x3
+    kernels only, so all zero from another kernel or an older library."""
+    base = nwg * iters * STRIDE + 4 * nwg
+    sw = a[base:base + nwg * iters].reshape(nwg, iters)[:, 1:Tn]
+    if sw.size == 0 or not np.all(sw > 0):
+        print('  gather sweeps: not recorded by this kernel')
+        return
+    print(f'  gather sweeps (iterations 1 ...): median {np.median(sw):.0f}  p90 {np.percentile(sw, 90):.0f}  '
+          f'max {sw.max()}  mean {sw.mean():.2f}')
 
 
 def arrival_spread(a, st, nwg, iters, Tn):
@@ -150,7 +164,7 @@ def arrival_spread(a, st, nwg, iters, Tn):
     across workgroups: their origins differ, even within one XCD.)"""
     base = nwg * iters * STRIDE
     m0, r0 = a[base:base + 2 * nwg:2].astype(np.float64), a[base + 1:base + 2 * nwg:2].astype(np.float64)
-    m1, r1 = a[base + 2 * nwg::2].astype(np.float64), a[base + 2 * nwg + 1::2].astype(np.float64)
+    m1, r1 = a[base + 2 * nwg:base + 4 * nwg:2].astype(np.float64), a[base + 2 * nwg + 1:base + 4 * nwg:2].astype(np.float64)
     if Tn < 2 or not (np.all(r1 > r0) and np.all(m1 > m0)):
         print('  barrier arrival spread: no valid end stamps (old library?) '
               f'm0 {m0[:3]} m1 {m1[:3]} r0 {r0[:3]} r1 {r1[:3]}')
