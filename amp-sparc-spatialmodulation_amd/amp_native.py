@@ -73,6 +73,14 @@ class AmpTrialsDecideArgs(C.Structure):
 RULE_SPARC, RULE_SEGMENTED = 0, 1
 
 
+class AmpSynthArgs(C.Structure):
+    _fields_ = [('seed', C.c_uint64), ('channel0', C.c_uint64), ('trial0', C.c_uint64),
+                ('sw', C.c_void_p), ('A', C.c_void_p), ('At', C.c_void_p),
+                ('Lh', C.c_int32), ('band_blocks', C.c_int32), ('noise_std', C.c_float), ('pad', C.c_int32),
+                ('x', C.c_void_p), ('sym', C.c_void_p), ('idx', C.c_void_p), ('y', C.c_void_p),
+                ('noise', C.c_void_p)]
+
+
 class AmpVampShard(C.Structure):
     _fields_ = [('xbuf', C.c_void_p), ('xbuf_bytes', C.c_size_t), ('B_global', C.c_int32), ('row_offset', C.c_int32),
                 ('gen', C.c_uint32), ('pad', C.c_int32)]
@@ -159,6 +167,9 @@ SIGNATURES = {
                                           _P]),
     'amp_vamp_trials_ch_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I, _I]),
     'amp_vamp_trials_ch_run': (C.c_int, [_D, _K, C.POINTER(AmpVampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _I, _P]),
+    # the trial batches' inputs drawn on the device (synth.py)
+    'amp_synth_channels': (C.c_int, [_D, C.POINTER(AmpSynthArgs), _I, _P]),
+    'amp_synth_trials': (C.c_int, [_D, _K, C.POINTER(AmpSynthArgs), _I, _I, _P]),
     'amp_bamp_workspace_bytes': (C.c_size_t, [_D, _I]),
     'amp_bamp_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),
     'amp_bamp_prepare': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),

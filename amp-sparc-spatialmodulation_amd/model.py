@@ -89,7 +89,7 @@ class Model(nn.Module):
     def __init__(self, config: Config, detector: str = 'vamp', path: str | None = None, amp=None,
                  seed: int | None = None, rng: str = 'host', group_epochs: bool = False,
                  shard: str = 'epochs', group_trials: int = 0, trial_channels: int = 0,
-                 trials_ws_limit: int = 4 << 30) -> None:
+                 trials_ws_limit: int = 4 << 30, synth_trials: bool = False) -> None:
         """rng='host' (default): the reference's numpy / torch-CPU random streams, bit for bit
         (parity mode).  rng='device': channel, messages and noise drawn on the GPU and the SVD
         on the GPU through the Gram matrix's eigendecomposition (svd_gram; throughput mode: same
@@ -114,6 +114,14 @@ class Model(nn.Module):
         library's workspace query stays under trials_ws_limit bytes (a setting; default 4 GiB: VAMP's
         three dense operators leave one channel per call at the published Nt = 1344 shape).
         A 'vamp' detector object without a true `trials_per_channel` attribute raises.
+        synth_trials (opt-in; needs rng='device', group_trials > 0 and config.B == 1, else ValueError):
+        the channels and the trials of every forward_trials call are drawn by TrialSynth (synth.py:
+        one launch for the call's channels, one for its trials' x / sym / idx / noise / y) and handed
+        over as stacks, VAMP's SVDs taken by svd_gram on the [G, n, N] stack.  Its stream is its own
+        (Philox, seed = this rank's seed; trial id = (SNR-point index << 32) + epoch number, channel
+        id = (point index << 32) + epoch // res), so the sweep's Losses do not depend on
+        group_trials / trial_channels; every call, a single trial included, goes through
+        forward_trials.  The channels' transposes count towards trials_ws_limit.
         shard (with torch.distributed): 'epochs' (default) gives each rank whole epochs with its
         own random stream and merges the metrics once per SNR point; 'trials' (SURVEY §8(e)
         exact-compat, VAMP / BAMP / SCAMP) gives every rank the SAME epochs (one seed) and splits each batch's
@@ -191,6 +199,16 @@ class Model(nn.Module):
             if shard == 'trials' or group_epochs:
                 raise ValueError('group_trials does not combine with group_epochs or trial sharding')
             self.trials_cap = int(group_trials)
+        self.synth = None
+        self._point = 0
+        if synth_trials:
+            if rng != 'device' or not self.trials_cap or config.B != 1:
+                raise ValueError("synth_trials: the trial batches' inputs are drawn on the device for "
+                                 "rng='device', group_trials > 0 and config.B == 1")
+            from synth import TrialSynth
+            if seed is None:
+                seed = int(np.random.SeedSequence().entropy % 2 ** 63)
+            self.synth = TrialSynth(config, seed + 7919 * self._stream_rank)
 
     # one epoch, in the reference's random-call order (vamp_model.py:55-61)
     def _epoch(self, SNR: float, new_channel: bool):
@@ -280,7 +298,9 @@ class Model(nn.Module):
         if k is None:
             k = max(1, min(self.channels_cap, self.trials_cap // res))
             query = getattr(self.amp, 'trials_workspace_bytes', None)
-            while k > 1 and query is not None and query(k * res, res) > self.trials_ws_limit:
+            # synth_trials: each channel's transpose At [N, n] c64 is held beside the operators
+            at = 8 * self.config.Nt * self.config.Lin * self.config.Nr * self.config.Lout if self.synth else 0
+            while k > 1 and query is not None and query(k * res, res) + k * at > self.trials_ws_limit:
                 k -= 1
             self._blocks_cap[res] = k
         return k
@@ -338,6 +358,50 @@ class Model(nn.Module):
             if new or not chans:
                 chans.append(self._svd if self.detector == 'vamp' else self._A)
         yield from flush()
+
+    def _synth_calls(self, ids: list, res: int) -> list:
+        """The forward_trials calls of the epochs `ids` under synth_trials: [(first epoch, trials,
+        first block, blocks)].  Without trial_channels (or with a block longer than trials_cap) a
+        call is a chunk of at most trials_cap epochs of one block; else up to _blocks_per_call(res)
+        whole blocks whose epochs and block numbers run on consecutively (TrialSynth's ids are
+        id0 + e and id0 + g), a short last block closing its call."""
+        calls = []
+        multi = self.channels_cap > 0 and res <= self.trials_cap
+        cap = self._blocks_per_call(res) if multi else 1
+        for i in ids:
+            blk = i // res
+            if calls:
+                e0, E, b0, G = calls[-1]
+                last = b0 + G - 1
+                if i == e0 + E and blk == last and (multi or E < self.trials_cap):
+                    calls[-1] = (e0, E + 1, b0, G)
+                    continue
+                if multi and i == e0 + E and blk == last + 1 and i % res == 0 and E == G * res and G < cap:
+                    calls[-1] = (e0, E + 1, b0, G + 1)
+                    continue
+            calls.append((i, 1, blk, 1))
+        return calls
+
+    def _group_synth(self, SNR: float, ids: list, res: int):
+        """The epochs `ids` (this rank's, in order) with every call's inputs drawn by TrialSynth: one
+        launch for the call's channels (kept while the next call continues the same block), one for
+        its trials, then forward_trials on the stacks.  Yields the epochs' Losses in order."""
+        point = self._point << 32
+        held = None                                   # (block, W, A [1, n, N], At, VAMP: (U, s, Vh))
+        for e0, E, b0, G in self._synth_calls(ids, res):
+            if G == 1 and held is not None and held[0] == b0:
+                _, W, A, At, svd = held
+            else:
+                W, A, At = self.synth.channels(G, point + b0)
+                svd = svd_gram(A) if self.detector == 'vamp' else None
+                held = (b0, W, A, At, svd) if G == 1 else None
+            x, sym, idx, y = self.synth.trials(At, E, res if G > 1 else E, SNR, point + e0)
+            per = {'per_channel': res} if G > 1 else {}
+            if self.detector == 'vamp':
+                ch = svd if G > 1 else tuple(f[0] for f in svd)
+            else:
+                ch = ((W,) if self.detector == 'scamp' else ()) + ((A,) if G > 1 else (A[0],))
+            yield from self.amp.forward_trials(*ch, y, SNR, x, sym, idx, **per)
 
     def _per_epoch_channels(self) -> bool:
         """Whether one launch may hold epochs with different channels (VAMP.epochs_channels_eligible)."""
@@ -398,7 +462,7 @@ class Model(nn.Module):
         EbN0dB_range = np.arange(start, final + step, step)
         SNRdB_range = EbN0dB_range + 10 * np.log10(self.rate)
         results = []
-        for SNRdB, EbN0dB in zip(SNRdB_range, EbN0dB_range):
+        for self._point, (SNRdB, EbN0dB) in enumerate(zip(SNRdB_range, EbN0dB_range)):
             if self.rank == 0:
                 print(f'EbN0dB={EbN0dB}')
             SNR = 10 ** (SNRdB / 10)
@@ -406,6 +470,9 @@ class Model(nn.Module):
             mine = [i for i in range(epochs) if (i // res) % self._epoch_world == self.rank % self._epoch_world]
             if self.group_cap > 1:
                 for loss in self._group(SNR, mine, res):      # side by side, chunks of group_cap epochs
+                    self.loss.accumulate(loss)
+            elif self.synth is not None:
+                for loss in self._group_synth(SNR, mine, res):    # inputs drawn per call on the device
                     self.loss.accumulate(loss)
             elif self.trials_cap > 0 and self.channels_cap > 0:
                 for loss in self._group_trial_channels(SNR, mine, res):   # several channels per call

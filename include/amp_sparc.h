@@ -626,6 +626,52 @@ size_t amp_vamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t k, int32_t 
 int amp_vamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_vamp_args* a,
                            const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream);
 
+/* ---- Input synthesis for the trial batches (throughput mode) — the channels of a forward_trials
+ *      call in one launch and its trials' x / sym / idx / noise / y in one launch, in place of the
+ *      per-epoch Channel.generate_as_sparc (channel.py:75-95), Data.segmented (data.py:74-91),
+ *      Channel.awgn (channel.py:103-116) and y = A x + n (vamp_model.py:60).  Same distributions,
+ *      its own random stream: Philox4x32-10 with key = (seed low, seed high 32 bits) and
+ *      counter = (index, id low, id high, stream); stream 0 taps, 1 message, 2 noise.  Every
+ *      draw is a pure function of (seed, stream, id, index): nothing depends on the grid, on how
+ *      trials are grouped into calls or on how many share one.  Unit normals from a block's words
+ *      w0, w1 (Box-Muller): u1 = ((w0 >> 9) + 0.5) 2^-23, u2 = (w1 >> 8) 2^-24, r = sqrt(-2 ln u1),
+ *      (re, im) = r (cos 2 pi u2, sin 2 pi u2), with the accurate logf / sincospif.
+ *      d describes ONE trial (d->B == 1); complex alphabets' layout (c64) throughout.  No
+ *      workspace.  AMP_E_ARG, before anything is launched: non-positive or inconsistent dims, M no
+ *      power of two, N odd, d->B != 1, K not in {1, 2, 4, 8, 16, 64}, null pointers, channels /
+ *      trials / per_channel < 1, more than 65535 channels, Lh outside [1, Lout], band_blocks
+ *      outside [0, Lout], Nr Nt Lh beyond 32 bits, L > 4096 (the trial's section list lives in LDS). */
+typedef struct amp_synth_args {
+    uint64_t seed;
+    uint64_t channel0;    /* amp_synth_channels: id of channel g is channel0 + g */
+    uint64_t trial0;      /* amp_synth_trials: id of trial e is trial0 + e */
+    const void* sw;       /* amp_synth_channels: f32 [Lout][Lin] sqrt(W) (channel.py:80-83, 61) */
+    void* A;              /* amp_synth_channels out: c64 [G][n][N] */
+    void* At;             /* c64 [G][N][n], A's plain (unconjugated) transpose: out of
+                           * amp_synth_channels, in of amp_synth_trials */
+    int32_t Lh;           /* amp_synth_channels: taps per antenna pair */
+    int32_t band_blocks;  /* amp_synth_trials: Lh > 0: a row of block o sums only the sections of
+                           * column blocks (o - Lh, o] (channels of amp_synth_channels /
+                           * generate_as_sparc); 0: every section (any A) */
+    float noise_std;      /* amp_synth_trials: sqrt(Na/Nr/SNR/2) (channel.py:153) */
+    int32_t pad;
+    void* x;              /* amp_synth_trials out: c64 [E][N] */
+    void* sym;            /* out int64 [E][L] gray labels (data.py:89) */
+    void* idx;            /* out int64 [E][L] flat nonzero indices, local to the trial (data.py:90) */
+    void* y;              /* out c64 [E][n] */
+    void* noise;          /* out c64 [E][n], or NULL */
+} amp_synth_args;
+/* A[g] and At[g], g < channels: tap (r, t, l) of channel id has index (r Nt + t) Lh + l,
+ * h = (re + i im) / sqrt(2 Na Lin) (channel.py:59); block (o, i) with l = o - i in [0, Lh) holds
+ * sw[o][i] h[:, :, l], every other block zeros. */
+int amp_synth_channels(const amp_dims* d, const amp_synth_args* a, int32_t channels, void* stream);
+/* Trial e (id trial0 + e) on channel e / per_channel, as amp_*_trials_ch_run.  Section s takes
+ * the block at index s: pos = mulhi32(w0, M), k = mulhi32(w1, K); x[s M + pos] = symbol k.  Row j
+ * takes the block at index j for its noise.  y[e][j] = sum over the active columns, in ascending
+ * section order, of At[g][col][j] symbol (float32, no contraction), plus the noise. */
+int amp_synth_trials(const amp_dims* d, const amp_constellation* c, const amp_synth_args* a, int32_t trials,
+                     int32_t per_channel, void* stream);
+
 /* ---- Element-wise shrinkage denoisers — replace Shrink (shrink.py:8-166).
  * r: [count] complex64 (is_complex != 0) or float32; cov: cov_vec [count] float32, or
  * cov_scalar when cov_vec is NULL (a 0-dim tensor in the reference).
