@@ -333,7 +333,9 @@ __device__ inline VampIter vamp_advance_head_pow2(const VampK& P, const VampIter
 // order with a select: an invalid term adds +0.0 to a sum that is never -0.0 (it starts at +0.0),
 // which leaves its bits (s2_lane holds 0 there: the discarded quotient is finite or inf).  eta's
 // two roundings come from the host (VampK.etaf / ometaf).
-__device__ inline void vamp_advance_tail(const VampK& P, VampIter& it, const S2Lane& sl) {
+// qout (optional): receives the four reciprocals 1 / (s^2 + vr) of columns lane + 64 j, for a caller
+// that hands them on (vamp_persist's one-wave tail: the w epilogue's scale of those columns).
+__device__ inline void vamp_advance_tail(const VampK& P, VampIter& it, const S2Lane& sl, float* qout = nullptr) {
     const float s2t = it.s2t;
     const float vr = (1.0f / s2t) * (float)P.noise_var;                                        // vamp.py:66
     const int lane = threadIdx.x & 63;
@@ -353,6 +355,10 @@ __device__ inline void vamp_advance_tail(const VampK& P, VampIter& it, const S2L
     it.inv1ma = 1.0f / (1.0f - alpha);
     it.sigma2 = sigma2;
     it.inv_sigma2 = 1.0f / sigma2;
+    if (qout) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) qout[j] = q[j];
+    }
 }
 
 __device__ inline amp_status vamp_make_status(const VampK& P, const VampIter& cur, const VampIter& nx, int fixed) {

@@ -52,8 +52,19 @@ constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iter
 #define AMP_X3_W8_POLL 2                // the eight-wave form's gather: 1 retries without a dependent abort-word load, 2 also
 #endif                                  // issues a sweep's loads together (A/B builds: 0, 1)
 #ifndef AMP_SCALAR_TAIL
-#define AMP_SCALAR_TAIL 1               // bf16x3 at one workgroup per CU: the LMMSE scalars of vamp_advance inside the
-#endif                                  // next iteration's GEMM1, behind group 0 (A/B builds: 0, the unsplit form)
+#define AMP_SCALAR_TAIL 2               // bf16x3 at one workgroup per CU: the LMMSE scalars of vamp_advance inside the
+#endif                                  // next iteration's GEMM1, behind group 0: 1 in every wave, 2 in one wave of the
+                                        // eight-wave form, handed on through LDS (the four-wave form: as 1); A/B builds:
+                                        // 0, the unsplit form, and 1
+#ifndef AMP_WAVE_TAIL_WAVE
+#define AMP_WAVE_TAIL_WAVE 0            // AMP_SCALAR_TAIL = 2: the wave that forms the tail (A/B builds: 4, a wave of the
+#endif                                  // SIMDs' second set: no better)
+#ifndef AMP_WAVE_TAIL_GROUP
+#define AMP_WAVE_TAIL_GROUP 0           // ... and the GEMM1 group it stands behind (A/B builds: 1, 2, 4: a shorter traced
+#endif                                  // GEMM1, but no faster step on every box)
+#ifndef AMP_WAVE_TAIL_ARRIVAL
+#define AMP_WAVE_TAIL_ARRIVAL 0         // trace builds only: w + 1 puts wave w's arrival at GEMM1's closing barrier in
+#endif                                  // the trace's slot 9 (0: the tail's end, as before)
 
 // LDS carve (floats).  Row strides 2N+4 / max(2N,2k)+4 keep the f32 engine's 16-row ds_read_b128
 // and accumulator stores conflict-free (row r and r+4 land 16 banks apart); the split-precision
@@ -156,6 +167,16 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // r_epi, inv_sigma2 for the denoiser) follow inside the next iteration's GEMM1 (DESIGN.md §3.1:
     // -3.6 to -10 us per cfg4 step, though the traced GEMM1 grows by the tail's length)
     constexpr int STAIL = (X3PF && OCC == 1) ? AMP_SCALAR_TAIL : 0;
+    // the eight-wave form (AMP_SCALAR_TAIL = 2): the tail's values are wave-uniform and the same in every
+    // wave, so one wave (TLW, behind group TLG) forms them and leaves the record {vr, alpha, inv1ma, sigma2,
+    // inv_sigma2} at scr[WT_REC ...] and its four reciprocals 1 / (s^2 + vr) per lane at scr[lane + 64 j]
+    // (all k = 256 columns); every wave reads the record behind GEMM1's closing barrier, and the w
+    // epilogue takes its columns' scale from the table instead of dividing again.  scr is free from the
+    // gather's second barrier to part_publish; the write stands behind the r~ build's closing barrier,
+    // the reads behind GEMM1's, the next write three barriers or more later: one slot, no flag.
+    constexpr bool WTAIL = STAIL == 2 && NWV == 8;
+    constexpr int TLW = AMP_WAVE_TAIL_WAVE, TLG = WTAIL ? AMP_WAVE_TAIL_GROUP : 0, WT_REC = 256;
+    static_assert(!WTAIL || (TLW < NWV && TLG < G3 && 8 * NT * NWV == 256), "one-wave tail: k = 256 columns, four per lane");
     // the eight-wave bf16x3 form at one workgroup per CU: the A operand's phases (r~ build, w store,
     // the GEMMs' fragment reads, r_epi) take the item split (amp_persist.h x3_store8_item) and the
     // geometry that N = k = 8 NT NWV fixes as constants, so that plane and row offsets are DS
@@ -338,6 +359,13 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
             if (wave == 0) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) s_s2[lane + 64 * j] = s2l.v[j];
+                // iteration 0's table and record, from vamp_first_iter's vr (read behind two barriers)
+                if constexpr (WTAIL) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) scr[lane + 64 * j] = 1.0f / (s2l.v[j] + cur.vr);
+                    *reinterpret_cast<float4*>(scr + WT_REC) = make_float4(cur.vr, cur.alpha, cur.inv1ma, cur.sigma2);
+                    scr[WT_REC + 4] = cur.inv_sigma2;
+                }
             }
         }
     }
@@ -637,7 +665,28 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 // vamp_first_iter), complete before the w epilogue reads cur.vr: behind group 0's MFMAs
                 // and the request of group 1's operators
                 // (behind group 1 in the SIMD's second wave, waves 4-7, it measured slower: DESIGN.md §3.1)
+                // (the one-wave form, WTAIL: wave TLW alone, which leaves the record and its reciprocals in
+                // scr; cur is every wave's copy of the record, read back behind the closing barrier.  Waves
+                // 0-3 reach that barrier ~3k cycles ahead of waves 4-7, with or without the tail)
+                const int wvu = WTAIL ? __builtin_amdgcn_readfirstlane(wave) : 0;
                 auto tail0 = [&](int g) __attribute__((always_inline)) {
+                    if constexpr (WTAIL) {
+                        if (g == TLG && t > 0 && wvu == TLW) {
+                            const int lnt = pl_opaque(lane);   // (addresses formed here, not hoisted)
+                            S2Lane s2x;
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) s2x.v[j] = s_s2[lnt + 64 * j];
+                            VampIter tl = cur;
+                            float q[4];
+                            vamp_advance_tail(P, tl, s2x, q);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) scr[lnt + 64 * j] = q[j];
+                            *reinterpret_cast<float4*>(scr + WT_REC) = make_float4(tl.vr, tl.alpha, tl.inv1ma, tl.sigma2);
+                            scr[WT_REC + 4] = tl.inv_sigma2;
+                            if (AMP_WAVE_TAIL_ARRIVAL == 0 && trc && lnt == 0 && t < P.max_iter)
+                                trc[((size_t)wg * P.max_iter + t) * AMP_TRACE_STRIDE + 9] = __builtin_amdgcn_s_memtime();
+                        }
+                    } else
                     if (g == 0 && t > 0) {
                         S2Lane s2x;
 #pragma unroll
@@ -710,8 +759,18 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 for (int r = 0; r < 4; ++r) s_hmax[wave][4 * (lane >> 4) + r] = mrow[r];
             }
         }
+        if constexpr (WTAIL && AMP_WAVE_TAIL_ARRIVAL != 0) {
+            if (trc && tid == 64 * (AMP_WAVE_TAIL_ARRIVAL - 1) && t < P.max_iter)
+                trc[((size_t)wg * P.max_iter + t) * AMP_TRACE_STRIDE + 9] = __builtin_amdgcn_s_memtime();
+        }
         __syncthreads();
         stamp(t, 2);
+        if constexpr (WTAIL) {
+            // the record of this iteration (iteration 0: the prologue's copy of vamp_first_iter's)
+            const float4 rec = *reinterpret_cast<const float4*>(scr + WT_REC);
+            cur.vr = rec.x; cur.alpha = rec.y; cur.inv1ma = rec.z; cur.sigma2 = rec.w;
+            cur.inv_sigma2 = scr[WT_REC + 4];
+        }
         if constexpr (H2 || I8) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -754,7 +813,11 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
 #pragma unroll
             for (int t2 = 0; t2 < NC; ++t2) {
                 const int o = 16 * (cc0 + t2) + (lnx & 15);
-                const float sc = 1.0f / (s2c[t2] + cur.vr);
+                // WTAIL: the tail wave's q of column o.  s2c[t2] is sv * sv of the same s[o] that s2_lane
+                // squares and vr the record's, so 1.0f / (s2c[t2] + cur.vr) has the same bits
+                float sc;
+                if constexpr (WTAIL) sc = scr[o];
+                else sc = 1.0f / (s2c[t2] + cur.vr);
                 float wr[4], wi[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {

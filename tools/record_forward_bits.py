@@ -5,6 +5,7 @@ tests/test_gpu_vamp_ring_prefill.py (tests/golden/ring_prefill_bits.part<k>.npz)
   python tools/record_forward_bits.py [--out DIR] [--stem STEM] [--cases "Nt,Na,Nr,B,alphabet;..."] [--share-channel]
                                       [--ebn0 "dB;..."] [--nan-row "row;..."] [--inf-entry "row,col;..."]
                                       [--scale-y "f;..."] [--dump] [--dump-wr]
+                                      [--tail] [--iters "n;..."] [--tags "tag;..."] [--forwards n]
 
 --stem / --cases record another fixture (tests/golden/<stem>.part<k>.npz) for another case list;
 --share-channel draws one channel, the first case's, stores it once ('shared/U', 's', 'Vh', 'SNR')
@@ -19,6 +20,13 @@ at the channel's: the logits grow with f, which drives a case into the exact-flo
 GEMM2 epilogue r per iteration: the first WR_FULL iterations whole ('f<i>_it_w', 'f<i>_it_r'
 [WR_FULL, B, 2N]), every iteration as one CRC-32 per trial row ('f<i>_it_wcrc', 'f<i>_it_rcrc' [T, B])
 and whether the row of w is finite ('f<i>_it_wfin');
+--tail runs every forward with the state dump on and stores, per iteration, one CRC-32 per trial row of the
+GEMM1 epilogue's w ('f<i>_it_wcrc' [T, B]; w carries vr and the LMMSE reciprocal of its column), whether the
+row is finite ('f<i>_it_wfin') and each workgroup's 1 / sigma2 as the denoiser took it ('f<i>_it_inv' [T, nwg]),
+and the status record's four scalars ('f<i>_last_scalar');
+--iters sets the iteration cap per case (one value: every case; an empty entry: 20);
+--tags appends '#<tag>' to a case's name in the fixture, so that one shape can be recorded several times
+(another cap, Eb/N0 or y); --forwards n records n forwards per case (the first builds, the others reuse);
 --dump runs the reuse forward with the persistent engine's per-iteration state dump on and stores,
 for the iterations it ran, every valid trial's var ('f1_it_var'), each wave's float64 var sum
 ('f1_it_wsum') and the exchange records the workgroups published ('f1_it_gran').
@@ -54,14 +62,14 @@ def case_name(Nt, Na, Nr, B, alphabet):
     return f'{alphabet}_{Nt}_{Na}_{Nr}_{B}'
 
 
-def config(Nt, Na, Nr, B, alphabet, device):
+def config(Nt, Na, Nr, B, alphabet, device, iterations=20):
     from config import Config
-    return Config(Nt, Na, Nr, 1, 1, batch=B, generator_mode='sparc', iterations=20, alphabet=alphabet,
+    return Config(Nt, Na, Nr, 1, 1, batch=B, generator_mode='sparc', iterations=iterations, alphabet=alphabet,
                   channel_profile='uniform', channel_truncation='tail', device=device)
 
 
-def make_inputs(case, shared=None, ebn0=None, nan_row=None, inf_entry=None, scale_y=None):
-    """One channel and two epochs of messages + noise (host tensors), in the reference's call order.
+def make_inputs(case, shared=None, ebn0=None, nan_row=None, inf_entry=None, scale_y=None, forwards=2):
+    """One channel and two (forwards) epochs of messages + noise (host tensors), in the reference's call order.
     shared: the make_inputs result of another case whose channel (A, U, s, Vh, SNR) this one uses;
     ebn0: this case's own Eb/N0 (else the alphabet's default, or the shared channel's SNR);
     nan_row: the row of y set to NaN in both epochs; inf_entry: the (row, column) of y set to +inf in both;
@@ -75,13 +83,13 @@ def make_inputs(case, shared=None, ebn0=None, nan_row=None, inf_entry=None, scal
     if shared is None:
         _, A = ch.generate_as_sparc()
         U, s, Vh = torch.linalg.svd(A, full_matrices=False)
-        SNR = c.snr(EBN0[case[4]])
+        SNR = c.snr(EBN0[case[4]] if ebn0 is None else ebn0)
     else:
         A, U, s, Vh, SNR = (shared[k] for k in ('A', 'U', 's', 'Vh', 'SNR'))
     if ebn0 is not None:
         SNR = c.snr(ebn0)
     eps = []
-    for _ in range(2):
+    for _ in range(forwards):
         x, sym, idx = da.generate_message()
         y = A @ x + ch.awgn(SNR)
         if scale_y is not None:
@@ -124,7 +132,7 @@ def row_crc(a):
     return np.array([[zlib.crc32(r.tobytes()) for r in it] for it in a], dtype=np.uint32).reshape(a.shape[:2])
 
 
-def dumped_forward(det, cfg, chan, SNR, ep, device, wr=False):
+def dumped_forward(det, cfg, chan, SNR, ep, device, wr=False, tail=False):
     """forward() with the persistent engine's state dump on (amp_vamp_debug_dump); adds, for the
     iterations that ran: it_var [T, B, N] float32, it_wsum [T, nwg, waves] float64 (each wave's var
     sum), it_gran [T, nwg, 8] uint32 (the exchange records: sumvar, notclose, tag, max|xi|, min max, 0, tag)."""
@@ -142,10 +150,16 @@ def dumped_forward(det, cfg, chan, SNR, ep, device, wr=False):
     T = int(out['T'][0])
     assert int(det.last.status().gemm) == 2, 'the dump is the persistent bf16x3 engine\'s'
     d = dump.cpu().numpy()
+    rows = [min(PBM, B - w * PBM) for w in range(nwg)]
+    if tail:   # slot 0: w; slot 3, row 1, column N: the 1 / sigma2 the denoiser of this workgroup took
+        w = np.concatenate([d[:T, g, 0, :rows[g]] for g in range(nwg)], axis=1)
+        out['it_wcrc'], out['it_wfin'] = row_crc(w), np.isfinite(w).all(axis=2)
+        out['it_inv'] = d[:T, :, 3, 1, N].copy()
+        out['last_scalar'] = np.array(list(det.last.status().last_scalar), dtype=np.float32)
+        return made, out
     off = (C.c_uint64 * 5)()
     nat.check(nat.lib().amp_vamp_debug_offsets(C.byref(cfg.dims()), N, ITERS, 1, off), 'amp_vamp_debug_offsets')
     gran = det.last.buf.ws[int(off[0]):int(off[0]) + ITERS * nwg * 32].cpu().numpy().view(np.uint32).reshape(ITERS, nwg, 8)
-    rows = [min(PBM, B - w * PBM) for w in range(nwg)]
     waves = 8 if N >= 256 else 4
     out['it_var'] = np.concatenate([d[:T, w, 3, :rows[w], :N] for w in range(nwg)], axis=1).copy()
     out['it_wsum'] = np.ascontiguousarray(d[:T, :, 3, 0, N:N + 2 * waves]).view(np.float64).copy()
@@ -158,13 +172,16 @@ def dumped_forward(det, cfg, chan, SNR, ep, device, wr=False):
     return made, out
 
 
-def run_case(case, inp, device, dump=False, wr=False):
+def run_case(case, inp, device, dump=False, wr=False, tail=False, iters=ITERS):
     """A building forward, then a reuse forward with a new y on the same channel objects
-    (dump: the reuse forward with the state dump on; wr: both, with w and r stored too)."""
+    (dump: the reuse forward with the state dump on; wr: both, with w and r stored too;
+    tail: every forward of inp, dumped as --tail says; iters: the iteration cap, at most ITERS)."""
     from vamp import VAMP
-    cfg = config(*case, device='cuda')
+    cfg = config(*case, device='cuda', iterations=iters)
     det = VAMP(cfg)
     chan = tuple(inp[k].to(device).contiguous() for k in ('U', 's', 'Vh'))
+    if tail:
+        return [dumped_forward(det, cfg, chan, inp['SNR'], ep, device, tail=True) for ep in inp['eps']]
     if wr:
         return [dumped_forward(det, cfg, chan, inp['SNR'], ep, device, wr=True) for ep in inp['eps']]
     res = [forward(det, chan, inp['SNR'], inp['eps'][0], device)]
@@ -223,6 +240,10 @@ def main():
     ap.add_argument('--inf-entry', default=None, help='"row,col;..." per case: that entry of y is +inf (empty: none)')
     ap.add_argument('--scale-y', default=None, help='"f;..." per case: y is multiplied by f (empty: 1)')
     ap.add_argument('--dump-wr', action='store_true', help="both forwards' per-iteration w and r (see above)")
+    ap.add_argument('--tail', action='store_true', help="every forward's per-iteration w CRCs and 1 / sigma2 (see above)")
+    ap.add_argument('--iters', default=None, help='"n;..." per case: the iteration cap (one value: every case; empty: 20)')
+    ap.add_argument('--tags', default=None, help='"tag;..." per case: the name\'s suffix in the fixture (empty: none)')
+    ap.add_argument('--forwards', type=int, default=2, help='forwards per case (the first builds)')
     ap.add_argument('--dump', action='store_true', help="the reuse forward's per-iteration var, wave sums and exchange records")
     args = ap.parse_args()
     cases = CASES if args.cases is None else [
@@ -248,14 +269,26 @@ def main():
         vals = args.scale_y.split(';')
         assert len(vals) == len(cases), (vals, cases)
         scales = [float(v) if v.strip() else None for v in vals]
+    iters = [ITERS] * len(cases)
+    if args.iters is not None:
+        vals = args.iters.split(';')
+        vals = vals * len(cases) if len(vals) == 1 else vals
+        assert len(vals) == len(cases), (vals, cases)
+        iters = [int(v) if v.strip() else ITERS for v in vals]
+        assert all(1 <= v <= ITERS for v in iters), iters
+    tags = [''] * len(cases)
+    if args.tags is not None:
+        tags = [v.strip() for v in args.tags.split(';')]
+        assert len(tags) == len(cases), (tags, cases)
     device = torch.device('cuda', 0)
     flat = {}
     shared = None
-    for case, eb, nr, ie, sc in zip(cases, ebn0, nan_rows, inf_entries, scales):
-        name = case_name(*case)
+    for case, eb, nr, ie, sc, it, tag in zip(cases, ebn0, nan_rows, inf_entries, scales, iters, tags):
+        name = case_name(*case) + (f'#{tag}' if tag else '')
+        assert f'{name}/f0_y' not in flat, f'{name}: recorded twice (--tags)'
         own = shared is not None and case[0:3:2] != shared['dims']   # another Nt, Nr: its own channel
-        inp = make_inputs(case, None if own else shared, eb, nr, ie, sc)
-        res = run_case(case, inp, device, args.dump, args.dump_wr)
+        inp = make_inputs(case, None if own else shared, eb, nr, ie, sc, args.forwards)
+        res = run_case(case, inp, device, args.dump, args.dump_wr, args.tail, it)
         print(name, 'prepares (building, reuse) per forward:', [m for m, _ in res],
               'T:', [int(o['T'][0]) for _, o in res], 'nan_state:', [int(o['nan_state'][0]) for _, o in res])
         if args.share_channel and shared is None:
