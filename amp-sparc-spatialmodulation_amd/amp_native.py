@@ -191,6 +191,7 @@ SIGNATURES = {
     'amp_map_decide_workspace_bytes': (C.c_size_t, [_D]),
     'amp_decide_debug_sections': (C.c_int, [_D, _K, _P, _P, _P, _I, _P, _P, _P, _P]),
     'amp_x3_planes_debug': (C.c_int, [_P, _I, _P, _P]),
+    'amp_x3_pack_store_debug': (C.c_int, [_P, _I, _P, _P]),
     'amp_exchange_reduce_debug': (C.c_int, [_P, _P, _I, _P, _P, _P, _P]),
     'amp_exchange_poll_debug': (C.c_int, [_P, _I, C.c_uint32, _I, _P, _P]),
     'amp_shrink_bayes': (C.c_int, [_K, C.c_int64, _I, _P, C.c_float, _P, C.c_float, C.c_float, _P, _P]),

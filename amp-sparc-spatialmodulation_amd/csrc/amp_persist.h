@@ -271,11 +271,19 @@ __device__ __forceinline__ float dpp_swap_pair_u(float v) {
 }
 
 // x3_store_acc in that form (one item = one accumulator tile: this lane's eight split values).
-template <int LDX>
-__device__ __forceinline__ void x3_store_acc_item(unsigned short* sP, int o, const float (&vr)[4], const float (&vi)[4]) {
+// One body in two halves.  The pack half (the DPP pair swap, the raw split, the masked fallback) turns
+// the tile into its 2 x 6 plane words (q[h][f]: row row0 + h, plane f) with no LDS access; the store
+// half writes them at the permuted columns.  PART 0 runs both back to back (x3_store_acc_item), 1 the
+// pack half alone, leaving the words in w, 2 the store half alone on the words in w: vamp_persist's w
+// epilogue packs ahead of GEMM1's closing barrier and stores behind it.
+template <int LDX, int PART>
+__device__ __forceinline__ void x3_acc_item_part(unsigned short* sP, int o, const float (&vr)[4], const float (&vi)[4],
+                                                 unsigned (*w)[6]) {
     static_assert(5 * 32 * LDX + 2 * LDX < 65536, "the plane and row offsets are DS immediates");
     const int lane = pl_opaque((int)threadIdx.x) & 63;
     const bool odd = (lane & 1) != 0;
+    unsigned q[2][6];
+    if constexpr (PART != 2) {
     float xr[2][2], xi[2][2];   // [h]: the column pair's (even, odd) values of row row0 + h
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -285,7 +293,6 @@ __device__ __forceinline__ void x3_store_acc_item(unsigned short* sP, int o, con
         xr[h][0] = odd ? gr : mr; xr[h][1] = odd ? mr : gr;
         xi[h][0] = odd ? gi : mi; xi[h][1] = odd ? mi : gi;
     }
-    unsigned q[2][6];
     f32x2_t s;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -300,6 +307,18 @@ __device__ __forceinline__ void x3_store_acc_item(unsigned short* sP, int o, con
             split3x2(xi[h][0], xi[h][1], q[h][3], q[h][4], q[h][5]);
         }
     }
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int f = 0; f < 6; ++f) q[h][f] = w[h][f];
+    }
+    if constexpr (PART == 1) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int f = 0; f < 6; ++f) w[h][f] = q[h][f];
+    } else {
     // rows row0, row0 + 1 (row0 even): the same permuted column unless the mask's low bit tells
     // them apart, so row0 + 1 keeps a column of its own
     const int row0 = 4 * (lane >> 4) + (odd ? 2 : 0);
@@ -310,6 +329,21 @@ __device__ __forceinline__ void x3_store_acc_item(unsigned short* sP, int o, con
 #pragma unroll
         for (int f = 0; f < 6; ++f) *reinterpret_cast<unsigned*>(p + f * 16 * LDX) = q[h][f];
     }
+    }
+}
+
+template <int LDX>
+__device__ __forceinline__ void x3_store_acc_item(unsigned short* sP, int o, const float (&vr)[4], const float (&vi)[4]) {
+    x3_acc_item_part<LDX, 0>(sP, o, vr, vi, nullptr);
+}
+template <int LDX>
+__device__ __forceinline__ void x3_pack_acc_item(const float (&vr)[4], const float (&vi)[4], unsigned (&w)[2][6]) {
+    x3_acc_item_part<LDX, 1>(nullptr, 0, vr, vi, w);
+}
+template <int LDX>
+__device__ __forceinline__ void x3_store_packed_item(unsigned short* sP, int o, unsigned (&w)[2][6]) {
+    const float none[4] = {0.f, 0.f, 0.f, 0.f};
+    x3_acc_item_part<LDX, 2>(sP, o, none, none, w);
 }
 
 // Scalar form (weight builder): the three pieces of one value.
@@ -380,13 +414,37 @@ __device__ __forceinline__ void x3_ring_fill(X3Ring<NT, x3_ring_depth(G, R)>& ri
 struct X3NoHook {
     __device__ __forceinline__ void operator()(int) const {}
 };
+// PRIO (vamp_persist's eight-wave form, two waves per SIMD: AMP_X3_GEMM_PRIO): the issue priority of this
+// wave while the GEMM runs, by the half it belongs to (half: wave-uniform, in an SGPR; 0 the SIMD's
+// older wave, 1 the younger).  0: none, no code.  1: the younger half at priority 1 throughout.  2: the
+// younger half at priority 1 for groups 0 .. G / 2 - 1.  3: priority 1 in alternate groups, the older
+// half in odd groups and the younger in even ones, flipped behind each group's refill requests.  Every
+// form leaves the GEMM at priority 0.  Only the time at which instructions issue differs.
+template <int PRIO, int G>
+__device__ __forceinline__ void x3_gemm_prio(int g, int half) {
+    if constexpr (PRIO != 0) {
+        // the priority of group g's MFMAs (g == G: the exit); s_setprio takes an immediate
+        const bool young = g < G && (PRIO == 1 || (PRIO == 2 && g < G / 2) || (PRIO == 3 && (g & 1) == 0));
+        const bool old = g < G && PRIO == 3 && (g & 1) == 1;
+        if (PRIO != 3 && g != 0 && g != (PRIO == 2 ? G / 2 : G)) return;   // no change at this group
+        if (half != 0) {
+            if (young) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+        } else if (PRIO == 3) {
+            if (old) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+        }
+    }
+}
+
 template <int NT, int G, int R = 1, bool PIN = false, bool HL = false, bool NEXT = false, class Hook = X3NoHook,
-          class After = X3NoHook>
+          class After = X3NoHook, int PRIO = 0>
 __device__ __forceinline__ void gemm_x3_ring(const unsigned short* sP, int ldx, const void* __restrict__ wq, int ct0,
                                              X3Ring<NT, x3_ring_depth(G, R)>& ring, f32x4 (&cr)[NT], f32x4 (&ci)[NT],
                                              const void* __restrict__ wq_next = nullptr, Hook&& hook = Hook(),
-                                             After&& after = After()) {
+                                             After&& after = After(), int half = 0) {
     constexpr int RR = x3_ring_depth(G, R);
+    x3_gemm_prio<PRIO, G>(0, half);
     static_assert(!NEXT || G % RR == 0, "the next operator's group j lands in slot j % RR");
     constexpr int NL = HL ? NT : 1;
     const int lane = threadIdx.x & 63;
@@ -461,6 +519,7 @@ __device__ __forceinline__ void gemm_x3_ring(const unsigned short* sP, int ldx, 
         } else if constexpr (NEXT) {
             x3_ring_load<NT, G>(ring, d, x3_wrsrc<G>(wq_next, ct0), g + RR - G);
         }
+        x3_gemm_prio<PRIO, G>(g + 1, half);
         after(g);
         __builtin_amdgcn_sched_barrier(0);
     }

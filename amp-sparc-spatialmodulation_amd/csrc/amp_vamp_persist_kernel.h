@@ -15,6 +15,7 @@
 namespace amp {
 
 constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iteration)
+constexpr int AMP_TRACE_SEAM = 24;     // AMP_WAVE_TAIL_ARRIVAL = 9: per wave, two arrivals and a fallback word
 #ifndef AMP_OCC2_PK
 #define AMP_OCC2_PK 0                   // 1: the packed denoiser also at two waves per SIMD (diagnostic builds)
 #endif
@@ -63,8 +64,21 @@ constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iter
 #define AMP_WAVE_TAIL_GROUP 0           // ... and the GEMM1 group it stands behind (A/B builds: 1, 2, 4: a shorter traced
 #endif                                  // GEMM1, but no faster step on every box)
 #ifndef AMP_WAVE_TAIL_ARRIVAL
-#define AMP_WAVE_TAIL_ARRIVAL 0         // trace builds only: w + 1 puts wave w's arrival at GEMM1's closing barrier in
-#endif                                  // the trace's slot 9 (0: the tail's end, as before)
+#define AMP_WAVE_TAIL_ARRIVAL 0         // trace builds only: w + 1 (1 ... 8) puts wave w's arrival at GEMM1's closing barrier
+#endif                                  // in the trace's slot 9, w + 11 (11 ... 18) its arrival at GEMM2 + r's (0: the tail's
+                                        // end, as before); 9: slot 9 as at 0, and every wave's arrival at both barriers and
+                                        // its pack-ahead fallbacks in the words behind the sweep counts (AMP_TRACE_SEAM
+                                        // per (workgroup, iteration): tools/trace_persist.py sizes the buffer for them)
+#ifndef AMP_W_PACK_AHEAD
+#define AMP_W_PACK_AHEAD 1              // the eight-wave form with the one-wave tail: a wave forms and packs its w right
+#endif                                  // behind its own GEMM1, ahead of the closing barrier, and stores behind it
+                                        // (A/B builds: 0 the order before; 2, 3: waves 0-3 / waves 4-7 only)
+#ifndef AMP_X3_GEMM_PRIO
+#define AMP_X3_GEMM_PRIO 3              // the same kernels: wave priority through GEMM1 (amp_persist.h x3_gemm_prio: 3,
+#endif                                  // the SIMD's two waves at priority 1 in alternate groups; A/B builds: 0, 1, 2)
+#ifndef AMP_X3_GEMM2_PRIO
+#define AMP_X3_GEMM2_PRIO AMP_X3_GEMM_PRIO   // ... and through GEMM2
+#endif
 
 // LDS carve (floats).  Row strides 2N+4 / max(2N,2k)+4 keep the f32 engine's 16-row ds_read_b128
 // and accumulator stores conflict-free (row r and r+4 land 16 banks apart); the split-precision
@@ -130,6 +144,30 @@ constexpr AopLayout aop_layout(int N) {
 // to scratch in the eight-wave cfg4 build.
 constexpr int KARG_DC_OFF = karg_second_offset<VampK, DecConst>();
 
+// The eight-wave bf16x3 form's one-wave tail (AMP_SCALAR_TAIL = 2), for the w epilogue on either side of
+// GEMM1's closing barrier (AMP_W_PACK_AHEAD).  The record of this iteration as the tail wave (iteration
+// 0: the prologue) left it at rec:
+__device__ __forceinline__ void wtail_record(const float* rec, VampIter& cur) {
+    const float4 v = *reinterpret_cast<const float4*>(rec);
+    cur.vr = v.x; cur.alpha = v.y; cur.inv1ma = v.z; cur.sigma2 = v.w;
+    cur.inv_sigma2 = rec[4];
+}
+// w = sc (y~ + vr q) - q of one accumulator tile (sc: the tail wave's reciprocal of this lane's column), and
+// its rows of the state dump where they are formed (dp: this lane's first row and column there, or null).
+__device__ __forceinline__ void wtail_form(float sc, float vr, const f32x4& qr4, const f32x4& qi4, const float (&ytr)[4],
+                                           const float (&yti)[4], float (&wr)[4], float (&wi)[4], float* dp, int ldd) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float qr = qr4[r], qi = qi4[r];
+        wr[r] = sc * (ytr[r] + vr * qr) - qr;
+        wi[r] = sc * (yti[r] + vr * qi) - qi;
+    }
+    if (dp) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { dp[r * ldd] = wr[r]; dp[r * ldd + 1] = wi[r]; }
+    }
+}
+
 template <int NT, int KK, int NWV, int DU, bool X3, int OCC = 1, bool H2 = false, bool I8 = false>
 __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_arg, DecConst dc_arg) {
     (void)P_arg;
@@ -173,7 +211,8 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // (all k = 256 columns); every wave reads the record behind GEMM1's closing barrier, and the w
     // epilogue takes its columns' scale from the table instead of dividing again.  scr is free from the
     // gather's second barrier to part_publish; the write stands behind the r~ build's closing barrier,
-    // the reads behind GEMM1's, the next write three barriers or more later: one slot, no flag.
+    // the reads behind GEMM1's, the next write three barriers or more later: one slot, no flag
+    // (AMP_W_PACK_AHEAD reads them ahead of GEMM1's barrier and adds one: WPA below).
     constexpr bool WTAIL = STAIL == 2 && NWV == 8;
     constexpr int TLW = AMP_WAVE_TAIL_WAVE, TLG = WTAIL ? AMP_WAVE_TAIL_GROUP : 0, WT_REC = 256;
     static_assert(!WTAIL || (TLW < NWV && TLG < G3 && 8 * NT * NWV == 256), "one-wave tail: k = 256 columns, four per lane");
@@ -187,6 +226,22 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // integer keys and the mean's quotient by a power of two as a scaling (amp_persist.h
     // part_publish_keys / part_gather_keys, amp_vamp.h vamp_advance_head_pow2); same bits
     constexpr bool XCH = X3PF && NWV == 8 && OCC == 1 && AMP_X3_W8_XCH;
+    // the same kernels: a wave forms w = sc (y~ + vr q) - q and packs it into its 24 plane words right
+    // behind its own GEMM1, ahead of the closing barrier (waves 0-3 reach it ~3k cycles before waves 4-7:
+    // they pack while the late half finishes, and the late half packs with no SIMD partner beside it);
+    // behind the barrier only the 24 LDS stores remain.  The record and the table are then read ahead of
+    // the barrier, so the tail wave raises a flag word behind them (scr[WT_FLAG], workgroup-scope release;
+    // nothing else writes that word): the iteration index.  Until then the word holds the iteration before's
+    // (the write stands behind the r~ build's closing barrier, the last read of the old value ahead of GEMM1's
+    // closing barrier one iteration earlier).  A wave reads it once behind its last group (acquire); if it
+    // does not show this iteration, the wave takes the order before for this iteration (record, pack and
+    // store behind the barrier): no wait.  Iteration 0's flag: the prologue, behind its copy of the record
+    // and ahead of a barrier of its own, so no word of an earlier launch is ever read.
+    constexpr int WPAM = (WTAIL && AOP) ? AMP_W_PACK_AHEAD : 0;
+    constexpr bool WPA = WPAM != 0;
+    constexpr int WT_FLAG = WT_REC + 5;
+    constexpr int PRIO1 = (WTAIL && AOP) ? AMP_X3_GEMM_PRIO : 0, PRIO2 = (WTAIL && AOP) ? AMP_X3_GEMM2_PRIO : 0;
+    constexpr bool SEAM = WTAIL && AOP && AMP_WAVE_TAIL_ARRIVAL == 9;
     // the same kernels: the gather's retry loop with the abort word's load and the clock read issued
     // with each sweep instead of behind a failed one, and a sweep's eight loads in flight together
     // (amp_persist.h part_gather_keys POLL)
@@ -365,10 +420,15 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                     for (int j = 0; j < 4; ++j) scr[lane + 64 * j] = 1.0f / (s2l.v[j] + cur.vr);
                     *reinterpret_cast<float4*>(scr + WT_REC) = make_float4(cur.vr, cur.alpha, cur.inv1ma, cur.sigma2);
                     scr[WT_REC + 4] = cur.inv_sigma2;
+                    if constexpr (WPA) scr[WT_FLAG] = __uint_as_float(0u);   // iteration 0's flag
                 }
             }
         }
     }
+    // pack-ahead reads the table, the record and the flag ahead of iteration 0's first barrier on its own path (a
+    // reuse forward has no r~ build at t = 0): every wave passes this barrier behind the prologue's writes, so
+    // whatever an earlier launch left in the flag word is gone before any wave reads it
+    if constexpr (WPA) __syncthreads();
     // Tracker (vamp.py:22-26): xmmse = p, r = 0 (so r~ = p at t = 0), var(prev) = 1
     {
         const float p = (float)P.sparsity;
@@ -683,7 +743,10 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                             for (int j = 0; j < 4; ++j) scr[lnt + 64 * j] = q[j];
                             *reinterpret_cast<float4*>(scr + WT_REC) = make_float4(tl.vr, tl.alpha, tl.inv1ma, tl.sigma2);
                             scr[WT_REC + 4] = tl.inv_sigma2;
-                            if (AMP_WAVE_TAIL_ARRIVAL == 0 && trc && lnt == 0 && t < P.max_iter)
+                            if constexpr (WPA)
+                                __hip_atomic_store(reinterpret_cast<unsigned*>(scr + WT_FLAG), (unsigned)t, __ATOMIC_RELEASE,
+                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+                            if ((AMP_WAVE_TAIL_ARRIVAL == 0 || AMP_WAVE_TAIL_ARRIVAL == 9) && trc && lnt == 0 && t < P.max_iter)
                                 trc[((size_t)wg * P.max_iter + t) * AMP_TRACE_STRIDE + 9] = __builtin_amdgcn_s_memtime();
                         }
                     } else
@@ -695,6 +758,10 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                         stamp(t, 9);
                     }
                 };
+                if constexpr (PRIO1 != 0)   // waves 4-7 are the SIMDs' second, younger set
+                    gemm_x3_ring<NC, G3, X3R, X3PIN, true, true, X3NoHook, decltype(tail0)&, PRIO1>(
+                        sP, CY.ldx, Wx1, cc0, wring, cr, ci, Wx2, X3NoHook(), tail0, wvu >> 2);
+                else
                 gemm_x3_ring<NC, G3, X3R, X3PIN, true, true>(sP, AOP ? CY.ldx : ldx, Wx1, cc0, wring, cr, ci, Wx2, X3NoHook(), tail0);
             } else
             gemm_x3_ring<NC, G3, X3R, X3PIN, true, true>(sP, AOP ? CY.ldx : ldx, Wx1, cc0, wring, cr, ci, Wx2);
@@ -759,7 +826,71 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 for (int r = 0; r < 4; ++r) s_hmax[wave][4 * (lane >> 4) + r] = mrow[r];
             }
         }
+        if constexpr (WPA) {   // the whole seam of these kernels: pack, barrier, store
+            unsigned wpk[NC][2][6];   // the packed w that crosses the barrier
+            bool ahead = false, tried = false;
+            const int wvp = __builtin_amdgcn_readfirstlane(wave);
+            tried = WPAM == 1 || (WPAM == 2 && wvp < 4) || (WPAM == 3 && wvp >= 4);
+            if (tried) {
+                const unsigned fl = __hip_atomic_load(reinterpret_cast<unsigned*>(scr + WT_FLAG), __ATOMIC_ACQUIRE,
+                                                      __HIP_MEMORY_SCOPE_WORKGROUP);
+                ahead = (unsigned)__builtin_amdgcn_readfirstlane((int)fl) == (unsigned)t;
+            }
+            if (ahead) {
+                wtail_record(scr + WT_REC, cur);
+                const int lnx = pl_opaque(lane);   // (addresses formed here, not hoisted)
+#pragma unroll
+                for (int t2 = 0; t2 < NC; ++t2) {
+                    const int o = 16 * (cc0 + t2) + (lnx & 15);
+                    float wr[4], wi[4];
+                    wtail_form(scr[o], cur.vr, cr[t2], ci[t2], yt[2 * t2], yt[2 * t2 + 1], wr, wi,
+                               P.dump ? P.dump + (((size_t)t * nwg + wg) * 5 + 0) * PBM * twoN + 4 * (lane >> 4) * twoN + 2 * o : nullptr, twoN);
+                    x3_pack_acc_item<CY.ldx>(wr, wi, wpk[t2]);
+                }
+            } else {
+                // q crosses the barrier in the same registers (so that not both q and the words are live there)
+#pragma unroll
+                for (int t2 = 0; t2 < NC; ++t2)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { wpk[t2][0][r] = __float_as_uint(cr[t2][r]); wpk[t2][1][r] = __float_as_uint(ci[t2][r]); }
+            }
+            if constexpr (SEAM) {
+                if (trc && lane == 0 && t < P.max_iter) {
+                    unsigned long long* sm = trc + (size_t)nwg * P.max_iter * (AMP_TRACE_STRIDE + 1) + 4 * nwg +
+                                             ((size_t)wg * P.max_iter + t) * AMP_TRACE_SEAM;
+                    sm[wave] = __builtin_amdgcn_s_memtime();
+                    sm[16 + wave] = (tried && !ahead) ? 1u : 0u;   // this wave took the order before
+                }
+            } else if constexpr (AMP_WAVE_TAIL_ARRIVAL >= 1 && AMP_WAVE_TAIL_ARRIVAL <= 8) {
+                if (trc && tid == 64 * (AMP_WAVE_TAIL_ARRIVAL - 1) && t < P.max_iter)
+                    trc[((size_t)wg * P.max_iter + t) * AMP_TRACE_STRIDE + 9] = __builtin_amdgcn_s_memtime();
+            }
+            __syncthreads();
+            stamp(t, 2);
+            const int lnx = pl_opaque(lane);   // (addresses formed here, not hoisted)
+            if (ahead) {   // formed and packed ahead of the barrier: the 24 stores
+#pragma unroll
+                for (int t2 = 0; t2 < NC; ++t2) x3_store_packed_item<CY.ldx>(sP, 16 * (cc0 + t2) + (lnx & 15), wpk[t2]);
+            } else {       // the flag did not show this iteration (or this wave does not pack ahead)
+                wtail_record(scr + WT_REC, cur);
+#pragma unroll
+                for (int t2 = 0; t2 < NC; ++t2) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { cr[t2][r] = __uint_as_float(wpk[t2][0][r]); ci[t2][r] = __uint_as_float(wpk[t2][1][r]); }
+                    const int o = 16 * (cc0 + t2) + (lnx & 15);
+                    float wr[4], wi[4];
+                    wtail_form(scr[o], cur.vr, cr[t2], ci[t2], yt[2 * t2], yt[2 * t2 + 1], wr, wi,
+                               P.dump ? P.dump + (((size_t)t * nwg + wg) * 5 + 0) * PBM * twoN + 4 * (lane >> 4) * twoN + 2 * o : nullptr, twoN);
+                    x3_store_acc_item<CY.ldx>(sP, o, wr, wi);
+                }
+            }
+        } else {   // (every other kernel: the order before, indented as the rest of the loop body)
         if constexpr (WTAIL && AMP_WAVE_TAIL_ARRIVAL != 0) {
+            if constexpr (SEAM) {
+                if (trc && lane == 0 && t < P.max_iter)
+                    trc[(size_t)nwg * P.max_iter * (AMP_TRACE_STRIDE + 1) + 4 * nwg + ((size_t)wg * P.max_iter + t) * AMP_TRACE_SEAM + wave] =
+                        __builtin_amdgcn_s_memtime();
+            } else if constexpr (AMP_WAVE_TAIL_ARRIVAL <= 8)
             if (trc && tid == 64 * (AMP_WAVE_TAIL_ARRIVAL - 1) && t < P.max_iter)
                 trc[((size_t)wg * P.max_iter + t) * AMP_TRACE_STRIDE + 9] = __builtin_amdgcn_s_memtime();
         }
@@ -847,6 +978,7 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 sA[(4 * (lane >> 4) + r) * lda + col] = sc * (yt[t2][r] + cur.vr * q) - q;
             }
         }
+        }   // (!WPA)
         __syncthreads();
         stamp(t, 3);
         kbase = karg_launder(kbase);
@@ -888,6 +1020,10 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { cr[t2][r] *= hsc[r]; ci[t2][r] *= hsc[r]; }
             }
+            if constexpr (PRIO2 != 0)
+                gemm_x3_ring<NC, G3, X3R, X3PIN, true, false, X3NoHook, X3NoHook, PRIO2>(
+                    sP, CY.ldx, Wx2, cc0, wring, cr, ci, nullptr, X3NoHook(), X3NoHook(), __builtin_amdgcn_readfirstlane(wave) >> 2);
+            else
             if constexpr (X3PF) gemm_x3_ring<NC, G3, X3R, X3PIN, true>(sP, AOP ? CY.ldx : ldx, Wx2, cc0, wring, cr, ci);
             if constexpr (AOP) {
                 // r_epi with the AOP constants: row stride and the x~ / r bases (one address register
@@ -928,6 +1064,15 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
                 sR[o] = (xt - cur.alpha * rt) * cur.inv1ma;
             }
         }
+        }
+        if constexpr (WTAIL && AMP_WAVE_TAIL_ARRIVAL >= 11 && AMP_WAVE_TAIL_ARRIVAL <= 18) {   // (one wave's, in slot 9)
+            if (trc && tid == 64 * (AMP_WAVE_TAIL_ARRIVAL - 11) && t < P.max_iter)
+                trc[((size_t)wg * P.max_iter + t) * AMP_TRACE_STRIDE + 9] = __builtin_amdgcn_s_memtime();
+        }
+        if constexpr (SEAM) {   // this wave's arrival at the barrier that closes GEMM2 + r
+            if (trc && lane == 0 && t < P.max_iter)
+                trc[(size_t)nwg * P.max_iter * (AMP_TRACE_STRIDE + 1) + 4 * nwg + ((size_t)wg * P.max_iter + t) * AMP_TRACE_SEAM + 8 + wave] =
+                    __builtin_amdgcn_s_memtime();
         }
         __syncthreads();
         // 4. denoiser (vamp.py:84)

@@ -365,6 +365,49 @@ int amp_x3_planes_debug(const void* rows, int32_t nrows, void* planes, void* str
     return AMP_OK;
 }
 
+// Diagnostic (amp_x3_pack_store_debug): the two halves of x3_store_acc_item as vamp_persist's w epilogue
+// runs them, on caller-supplied rows in amp_x3_planes_debug's accumulator map: every wave packs its two
+// tiles (x3_pack_acc_item), the workgroup meets at a barrier, every wave stores the words it holds
+// (x3_store_packed_item).  The planes are copied out in LDS order: form 3 of amp_x3_planes_debug, bit for bit.
+namespace amp {
+
+__global__ __launch_bounds__(XPD_WG) void x3_pack_store_debug_kernel(const float* __restrict__ rows, int nrows,
+                                                                      unsigned* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    unsigned short* sP = reinterpret_cast<unsigned short*>(lds);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned w[2][2][6];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int o = 16 * (2 * wave + t) + (lane & 15);
+        float vr[4], vi[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 4 * (lane >> 4) + r;
+            const float2 v = *reinterpret_cast<const float2*>(rows + ((size_t)min(row, nrows - 1) * XPD_N + o) * 2);
+            vr[r] = row < nrows ? v.x : 0.f; vi[r] = row < nrows ? v.y : 0.f;
+        }
+        x3_pack_acc_item<XPD_N>(vr, vi, w[t]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 2; ++t) x3_store_packed_item<XPD_N>(sP, 16 * (2 * wave + t) + (lane & 15), w[t]);
+    __syncthreads();
+    for (int e = tid; e < XPD_WORDS; e += XPD_WG) out[e] = reinterpret_cast<const unsigned*>(sP)[e];
+}
+
+}  // namespace amp
+
+int amp_x3_pack_store_debug(const void* rows, int32_t nrows, void* planes, void* stream) {
+    using namespace amp;
+    AMP_REQUIRE(rows && planes, "amp_x3_pack_store_debug: null pointer argument");
+    AMP_REQUIRE(nrows >= 1 && nrows <= PBM, "amp_x3_pack_store_debug: nrows = %d (1 ... %d)", nrows, PBM);
+    hipLaunchKernelGGL(x3_pack_store_debug_kernel, dim3(1), dim3(XPD_WG), (size_t)XPD_WORDS * 4, (hipStream_t)stream,
+                       (const float*)rows, (int)nrows, (unsigned*)planes);
+    AMP_LAUNCH_CHECK("amp_x3_pack_store_debug");
+    return AMP_OK;
+}
+
 // Diagnostic (amp_exchange_reduce_debug): the reduction chain of vamp_persist's exchange on
 // caller-supplied values, today's forms and the key forms of the eight-wave bf16x3 kernel side by
 // side.  One workgroup of eight waves: part_publish and part_publish_keys on one PartAcc per thread

@@ -503,6 +503,10 @@ int amp_decide_debug_sections(const amp_dims* d, const amp_constellation* c, con
  * column j ^ 8 (r & 15)): form 0 the shared row-item writer (x3_store8), 1 the eight-wave engine's
  * item form of it, 2 the shared accumulator-layout writer (x3_store_acc), 3 its item form. */
 int amp_x3_planes_debug(const void* rows, int32_t nrows, void* planes, void* stream);
+/* Diagnostic: form 3 of amp_x3_planes_debug written in its two halves, as the eight-wave engine's w
+ * epilogue runs them: every wave packs its tiles into plane words, a barrier, every wave stores its
+ * words.  rows as above; planes: uint16 [6][16][256], equal to form 3 bit for bit. */
+int amp_x3_pack_store_debug(const void* rows, int32_t nrows, void* planes, void* stream);
 /* Diagnostic: the reduction chain of the persistent VAMP engine's per-iteration exchange on
  * caller-supplied values, in one workgroup of eight waves: the shared forms (float64 NaN-propagating
  * extremes, the IEEE division of the mean) and the eight-wave bf16x3 kernel's forms (extremes on

@@ -21,6 +21,8 @@ import torch        # noqa: E402
 
 PHASES = ['r~ build', 'GEMM1', 'w store', 'GEMM2 + r', 'denoiser', 'partial publish', 'partial gather', 'scalars']
 STRIDE = 10   # stamps per (workgroup, iteration): amp_vamp_persist.hip AMP_TRACE_STRIDE
+SEAM = 24     # AMP_TRACE_SEAM: per (workgroup, iteration) eight arrivals at GEMM1's closing barrier, eight at
+              # GEMM2's, eight pack-ahead fallback words (libraries built with AMP_WAVE_TAIL_ARRIVAL=9 only)
 # stamp slots in time order.  The exchange's three phases: slot 8 (this wave's denoiser done) -> 5 is the
 # partial publish (wave tree, both barriers, thread 0's fold and granule stores: it waits for the SIMD's
 # partner wave), 5 -> 6 the gather (sweep, lane fold, tree, LDS broadcast), 6 -> 7 the scalars (the all-NaN
@@ -103,7 +105,8 @@ def main():
     T = det.detect(inp['U'], inp['s'], inp['Vh'], inp['y'], inp['SNR'])
     nwg = (B + 15) // 16
     # ten stamps per (workgroup, iteration), 4 nwg start / end clock words, then the gathers' sweep counts
-    tr = torch.zeros(nwg * iters * STRIDE + 4 * nwg + nwg * iters, dtype=torch.int64, device=dev)
+    # (and the seam words of an AMP_WAVE_TAIL_ARRIVAL=9 library)
+    tr = torch.zeros(nwg * iters * STRIDE + 4 * nwg + nwg * iters + nwg * iters * SEAM, dtype=torch.int64, device=dev)
     s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s0.record()
     b0 = nat.prepare_counts()
@@ -140,7 +143,28 @@ def main():
         print(f'  scalars: gather end -> advance start median {np.median(raw[:, :, 9] - raw[:, :, 6]):.0f}, '
               f'vamp_advance median {np.median(raw[:, :, 7] - raw[:, :, 9]):.0f} cycles')
     sweep_counts(a, nwg, iters, Tn)
+    seam_arrivals(a, nwg, iters, Tn)
     arrival_spread(a, st, nwg, iters, Tn)
+
+
+def seam_arrivals(a, nwg, iters, Tn):
+    """Each wave's arrival at the barrier that closes GEMM1 (cycles behind stamp 1) and at the one that
+    closes GEMM2 + r (behind stamp 3), and the waves that did not pack their w ahead of the barrier
+    (the flag did not show the iteration yet).  Written by an AMP_WAVE_TAIL_ARRIVAL=9 library only."""
+    base = nwg * iters * STRIDE + 4 * nwg + nwg * iters
+    sm = a[base:base + nwg * iters * SEAM].reshape(nwg, iters, SEAM).astype(np.int64)[:, 1:Tn]
+    raw = a[:nwg * iters * STRIDE].reshape(nwg, iters, STRIDE).astype(np.int64)[:, 1:Tn]
+    if sm.size == 0 or not np.all(sm[:, :, :16] > 0):
+        print('  seam arrivals: not recorded by this library')
+        return
+    for name, lo, s0, s1 in (('GEMM1', 0, 1, 2), ('GEMM2 + r', 8, 3, 4)):
+        arr = np.median(sm[:, :, lo:lo + 8] - raw[:, :, s0, None], axis=(0, 1))
+        # stamp s1 is thread 0's, behind the barrier (GEMM2 + r: behind the argument reload as well)
+        print(f'  arrival at the barrier closing {name} (median cycles into the phase, waves 0-7): '
+              + ' '.join(f'{v:.0f}' for v in arr) + f'  of {np.median(raw[:, :, s1] - raw[:, :, s0]):.0f}')
+    fb = a[base:base + nwg * iters * SEAM].reshape(nwg, iters, SEAM)[:, :Tn, 16:24]
+    print(f'  pack-ahead fallbacks: {int(fb.sum())} of {fb.size} (wave, workgroup, iteration); iteration 0: {int(fb[:, 0].sum())}; '
+          f'per wave: {[int(v) for v in fb.sum(axis=(0, 1))]}')
 
 
 def sweep_counts(a, nwg, iters, Tn):
