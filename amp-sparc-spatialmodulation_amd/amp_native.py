@@ -132,6 +132,7 @@ SIGNATURES = {
     'amp_vamp_debug_prepare_counts': (C.c_int, [C.POINTER(C.c_uint64)]),
     'amp_vamp_epochs_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I]),
     'amp_vamp_debug_offsets': (C.c_int, [_D, _I, _I, _I, C.POINTER(C.c_uint64)]),
+    'amp_vamp_debug_launch_offsets': (C.c_int, [_D, _I, _I, C.POINTER(C.c_uint64)]),
     'amp_vamp_debug_dump': (C.c_int, [_P]),
     'amp_vamp_max_epochs': (C.c_int, [_D, _I]),
     'amp_vamp_max_epochs_gemm': (C.c_int, [_D, _I, _I]),

@@ -182,7 +182,15 @@ struct ALoadPair {
 // every nonzero weight of this column tile (multiples of GBK; weight_kband), default all of it:
 // a block-banded operator (the ISI / spatially coupled channel, channel.py:75-95) skips its
 // all-zero blocks.
-template <int BN, class AL, int KC = GKC>
+// SEG > 0 (VAMP's launch engine: gemm_store_kernel 2, GEMM2 1): a reduction of more than SEG chunks
+// is summed chunk by chunk, each chunk from a zeroed accumulator, and the chunk sums are added up.
+// One accumulator chained through all of a reduction (a dependent float32 addition per two floats)
+// erred at VAMP's y~ with n = 1024 (2048 floats) by 4.1x numpy's complex64 product in rms and 7.9x
+// in max, and GEMM2 at k = 512 (1024 floats) by 3.07x in its worst 32 x 64 block
+// (tests/test_gpu_vamp_launch_iter.py); a chain ends after 256 additions this way.  Up to SEG chunks
+// the one chain stays, and with it every bit of those results (gemm_store_kernel also forms the
+// persistent f32 engine's y~, n <= 512: two chunks).  0: one chain whatever the length.
+template <int BN, class AL, int KC = GKC, int SEG = 0>
 __device__ __forceinline__ void gemm_tile(const AL& al, const float* __restrict__ wp, int kap, int row0,
                                           int col0, float* lds, int kb = 0, int ke = -1) {
     using C = GemmCfg<BN, KC>;
@@ -204,6 +212,14 @@ __device__ __forceinline__ void gemm_tile(const AL& al, const float* __restrict_
 
     if (ke < 0) ke = kap;
     const int glast = (ke >> 3) - 1;   // last group of the range
+    const bool seg = SEG > 0 && ke - kb > SEG * KC;
+    f32x16 tot[SEG > 0 ? C::NACC : 1];
+    if constexpr (SEG > 0) {
+#pragma unroll
+        for (int j = 0; j < C::NACC; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tot[j][r] = 0.f;
+    }
     // The W ring runs across the chunks: a slot refilled GRING groups ahead past the end of a
     // chunk already holds the next chunk's group (every chunk is a whole number of rings), so a
     // chunk starts without waiting on its first operator loads.
@@ -246,6 +262,17 @@ __device__ __forceinline__ void gemm_tile(const AL& al, const float* __restrict_
     for (int kc0 = kb; kc0 < ke; kc0 += KC) {
         const int kc = min(KC, ke - kc0);
         const int g0 = kc0 >> 3, gc = kc >> 3;   // gc % GRING == 0 (kap % 64 == 0)
+        if constexpr (SEG > 0) {
+            if (seg && kc0 > kb) {   // the chunk before this one is a finished sum
+#pragma unroll
+                for (int j = 0; j < C::NACC; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        tot[j][r] += acc[j][r];
+                        acc[j][r] = 0.f;
+                    }
+            }
+        }
         if constexpr (PF) {
             __syncthreads();   // this chunk's LDS stores are visible
             if (kc0 + KC < ke) load_chunk(kc0 + KC, nxt, 0, PER);
@@ -296,6 +323,14 @@ __device__ __forceinline__ void gemm_tile(const AL& al, const float* __restrict_
                 __syncthreads();   // every wave is done with this chunk
                 store_chunk(kc0 + KC, nxt, 0, PER);
             }
+        }
+    }
+    if constexpr (SEG > 0) {
+        if (seg) {
+#pragma unroll
+            for (int j = 0; j < C::NACC; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[j][r] += tot[j][r];
         }
     }
     __syncthreads();   // the C tile aliases the A block

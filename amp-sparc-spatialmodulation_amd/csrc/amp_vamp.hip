@@ -56,7 +56,7 @@ __global__ __launch_bounds__(AMP_WG) void vamp_k2(VampK P, int t) {
     if (g.it.stopped) return;
     const GemmTile tile = xcd_tile();
     const int row0 = tile.rb * GBM, col0 = tile.cb * BN;
-    gemm_tile<BN>(ALoadPlain{P.w, P.wld, P.B, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
+    gemm_tile<BN, ALoadPlain, GKC, VAMP_SEG2>(ALoadPlain{P.w, P.wld, P.B, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
     const int nrows = min(GBM, P.B - row0), ncols = min(BN, 2 * P.N - col0);
     vamp_r_epilogue<BN>(P, g, lds, row0, col0, nrows, ncols);
     // the denoiser over the whole tile; the workgroup's partial at its linear index
@@ -527,6 +527,7 @@ int amp_vamp_run_sharded(const amp_dims* d, const amp_constellation* c, const am
     AMP_REQUIRE(allreduce_hook_set(), "amp_vamp_run_sharded: no all-reduce hook registered (amp_set_allreduce_hook)");
     AMP_REQUIRE(B_global >= d->B, "amp_vamp_run_sharded: B_global = %d < this rank's B = %d", B_global, d->B);
     P.Bmean = B_global;
+    P.x3 = 0;   // the launch engine runs f32 tiles whatever a->gemm asks for: amp_status.gemm says so
     hipStream_t st = (hipStream_t)stream;
     rc = vamp_prepare_impl(P, a, st);
     bool hook_failed = false;
@@ -598,6 +599,7 @@ int amp_vamp_prepare(const amp_dims* d, const amp_constellation* c, const amp_va
     Const64 c64;
     int rc = vamp_setup(d, c, a, P, c64);
     if (rc) return rc;
+    P.x3 = 0;   // the launch engine runs f32 tiles whatever a->gemm asks for: amp_status.gemm says so
     return vamp_prepare_impl(P, a, (hipStream_t)stream);
 }
 
@@ -609,6 +611,7 @@ int amp_vamp_iterate(const amp_dims* d, const amp_constellation* c, const amp_va
     AMP_REQUIRE(t >= 0 && t < a->max_iter, "amp_vamp_iterate: t = %d outside [0, %d)", t, a->max_iter);
     rc = vamp_attrs();
     if (rc) return rc;
+    P.x3 = 0;   // the launch engine runs f32 tiles whatever a->gemm asks for: amp_status.gemm says so
     return vamp_iterate_impl(P, c64, t, (hipStream_t)stream);
 }
 
@@ -617,6 +620,7 @@ int amp_vamp_finalize(const amp_dims* d, const amp_constellation* c, const amp_v
     Const64 c64;
     int rc = vamp_setup(d, c, a, P, c64);
     if (rc) return rc;
+    P.x3 = 0;   // the launch engine runs f32 tiles whatever a->gemm asks for: amp_status.gemm says so
     return vamp_finalize_impl(P, (hipStream_t)stream);
 }
 
@@ -639,6 +643,7 @@ int amp_vamp_run_reuse(const amp_dims* d, const amp_constellation* c, const amp_
         if (rc) return rc;
         return vamp_persist_launch(P, c64, DecConst{}, st, ncu);
     }
+    P.x3 = 0;   // the launch engine runs f32 tiles whatever a->gemm asks for: amp_status.gemm says so
     rc = vamp_prepare_impl(P, a, st);
     if (rc) return rc;
     for (int t = 0; t < P.max_iter; ++t) {
@@ -724,6 +729,16 @@ int amp_vamp_debug_offsets(const amp_dims* d, int32_t k, int32_t max_iter, int32
     out[2] = (uint64_t)((char*)w.pbar - base);
     out[3] = (uint64_t)((char*)w.dwg - base);
     out[4] = (uint64_t)((char*)w.ytil - base);
+    return AMP_OK;
+}
+
+int amp_vamp_debug_launch_offsets(const amp_dims* d, int32_t k, int32_t max_iter, uint64_t* out) {
+    if (!d || !out || k <= 0 || max_iter <= 0) return AMP_E_ARG;
+    char* const base = reinterpret_cast<char*>(uintptr_t{4096});   // a dummy base: offsets only
+    const VampWs w = vamp_carve(d, k, max_iter, base);
+    out[0] = (uint64_t)((char*)w.w - base);
+    out[1] = (uint64_t)vamp_wld(k);
+    out[2] = (uint64_t)((char*)w.var1 - base);
     return AMP_OK;
 }
 

@@ -16,6 +16,10 @@
 
 namespace amp {
 
+// GEMM2 of both engines (vamp_k2, tvamp_k2): a reduction over more than one 512-float chunk (k > 256,
+// launch-engine shapes only) is summed per chunk (amp_gemm.h gemm_tile SEG)
+constexpr int VAMP_SEG2 = 1;
+
 // ---- record guards: AllRows / LiveRows (amp_trials.h) that also hand out row rho's scalars ----
 // (PSCR is theirs, kept for the interface: VAMP's epilogues stage nothing past the C tile.)
 // The batch engine: the one record of iteration t, by value, for every row.  live() is a constant

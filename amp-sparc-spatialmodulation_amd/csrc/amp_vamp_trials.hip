@@ -138,7 +138,7 @@ __global__ __launch_bounds__(AMP_WG) void tvamp_k2(VampK P, CH ch, int t, const 
     const int row0 = ct.row0, col0 = tile.cb * BN;
     if (!tvamp_enter(P, ch, ct, nstop, s_it)) return;
     const VampLiveRows g{s_it};
-    gemm_tile<BN>(ALoadPlain{P.w, P.wld, ct.lim, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
+    gemm_tile<BN, ALoadPlain, GKC, VAMP_SEG2>(ALoadPlain{P.w, P.wld, ct.lim, P.wld}, P.Wt2, P.kap2, row0, col0, lds);
     const int nrows = min(GBM, ct.lim - row0), ncols = min(BN, 2 * P.N - col0);
     vamp_r_epilogue<BN>(P, g, lds, row0, col0, nrows, ncols);
     // the denoiser row by row, the row's own partial in the slot its B = 1 forward stores it to

@@ -391,7 +391,7 @@ __global__ __launch_bounds__(AMP_WG) void gemm_store_kernel(const float* __restr
     CH.per = per; CH.tpg = tpg;
     const ChannelTile ct = CH.tile(tile.rb, rows);
     const int row0 = ct.row0, col0 = tile.cb * BN;
-    gemm_tile<BN>(AL{a, lda, ct.lim, ka}, wt + (size_t)ct.g * dg, kap, row0, col0, lds);
+    gemm_tile<BN, AL, GKC, 2>(AL{a, lda, ct.lim, ka}, wt + (size_t)ct.g * dg, kap, row0, col0, lds);
     using C = GemmCfg<BN>;
     for (int e = threadIdx.x; e < GBM * BN; e += AMP_WG) {
         const int rho = e / BN, cc = e % BN;

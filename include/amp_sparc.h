@@ -306,6 +306,12 @@ size_t amp_vamp_epochs_workspace_bytes(const amp_dims* d, int32_t k, int32_t max
  * rare-path float64 words, out[2] the barrier words, out[3] the per-workgroup counter records,
  * out[4] y~ ([epochs * B][2k] floats; also the single-forward workspace's, epochs = 1). */
 int amp_vamp_debug_offsets(const amp_dims* d, int32_t k, int32_t max_iter, int32_t epochs, uint64_t* out);
+/* Diagnostic: where the launch engine keeps GEMM2's A operand in the single-forward workspace
+ * (amp_vamp_workspace_bytes): out[0] the byte offset of w ([B][wld] floats, re / im interleaved,
+ * columns < 2k the value w = scale (y~ + vr q) - q of the last iteration run, the rest a zero pad),
+ * out[1] wld in floats (2k rounded up to 4), out[2] the byte offset of var1 ([B][N], the var of
+ * odd iterations).  Three words. */
+int amp_vamp_debug_launch_offsets(const amp_dims* d, int32_t k, int32_t max_iter, uint64_t* out);
 /* Diagnostic: every later persistent VAMP launch of this process writes its per-iteration state
  * to buf (device, float32: [max_iter][nwg][5][16][2N]: w after GEMM1's epilogue, r after GEMM2's,
  * xmmse after the denoiser, then var (columns < N) and the waves' float64 var sums (row 0,

@@ -27,7 +27,6 @@ these shapes were taken.
 """
 import ctypes as C
 import functools
-import threading
 
 import numpy as np
 import pytest
@@ -220,83 +219,14 @@ def test_wide_batch_point(device, name):
             assert gio.bits_equal(a, b), key
 
 
-class _Exchange:
-    """The all-reduce of two slices detected by two threads of one process: each thread's hook puts
-    its float64 words on the host, the threads meet, each takes the reduction of both."""
-
-    def __init__(self, world):
-        self.local = threading.local()
-        self.barrier = threading.Barrier(world, timeout=60)
-        self.slots = [None] * world
-
-    def allreduce(self, buf, count, op):
-        import amp_native as nat
-        ws = self.local.det._ws
-        off = int(buf) - ws.data_ptr()
-        assert 0 <= off and off + 8 * count <= ws.numel()
-        view = ws[off:off + 8 * count].view(torch.float64)
-        self.slots[self.local.rank] = view.cpu()           # after the slice's launches on its stream
-        self.barrier.wait()
-        both = torch.stack(self.slots)
-        tot = both.sum(0) if op == nat.ALLREDUCE_SUM else torch.where(torch.isnan(both).any(0), both.sum(0),
-                                                                      both.max(0).values)
-        self.barrier.wait()                                # both have read the slots
-        view.copy_(tot)
-
-
 @pytest.mark.parametrize('name', ['batch_OOK_Nt16', 'batch_8PSK_Nt168'])
 def test_wide_sharded_slices_equal_whole_batch(device, monkeypatch, name):
     """batch_OOK_Nt16: k = 35 (w's rows padded); batch_8PSK_Nt168: k = 292, 2N = 1008 (partial last tile)."""
-    import amp_native as nat
+    import shard_threads
     from loss import counts_to_vector
-    from vamp import ShardedVAMP
     whole, _ = whole_batch(name)
-    inp = wi.device_inputs(name)
-    xch = _Exchange(2)
-    workspace_type = type(nat.WORKSPACE)
-
-    class PerThreadWorkspace:                              # one workspace cache per slice
-        def get(self, dev, key, nbytes):
-            if not hasattr(xch.local, 'ws'):
-                xch.local.ws = workspace_type()
-            return xch.local.ws.get(dev, key, nbytes)
-
-    monkeypatch.setattr(nat, 'WORKSPACE', PerThreadWorkspace())
-
-    class Slice(ShardedVAMP):
-        bounds = (0, 0)
-
-        def shard(self):
-            return self.bounds
-
-        def _allreduce(self, buf, count, op, stream, ctx):
-            try:
-                xch.allreduce(buf, count, op)
-                return 0
-            except Exception as e:   # noqa: BLE001 — reported by _run_hooked
-                self._hook_error = self._hook_error or e
-                return 1
-
-    out, errs = [None, None], []
-
-    def run(rank):
-        try:
-            with torch.cuda.device(inp['y'].device):
-                det = Slice(wi.config_of(name, device='cuda'))
-                det.bounds = (24 * rank, 24 * rank + 24)
-                xch.local.rank, xch.local.det = rank, det
-                L = det(inp['U'], inp['s'], inp['Vh'], inp['y'], inp['SNR'], inp['x'], inp['sym'], inp['idx'])
-                out[rank] = (int(L.last_status.T), counts_to_vector(L.last_counts))
-        except Exception as e:   # noqa: BLE001
-            errs.append((rank, repr(e)))
-            xch.barrier.abort()
-
-    threads = [threading.Thread(target=run, args=(r,)) for r in range(2)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    assert not errs, errs
+    out = shard_threads.run_slices(monkeypatch, lambda: wi.config_of(name, device='cuda'), wi.device_inputs(name),
+                                   lambda det, L: (int(L.last_status.T), counts_to_vector(L.last_counts)))
     assert out[0][0] == out[1][0] == whole[0], (out[0][0], out[1][0], whole[0])
     both = out[0][1] + out[1][1]
     # the nine integer counters exactly; the four float64 error sums up to their summation order
