@@ -70,13 +70,13 @@ class AmpTrialsDecideArgs(C.Structure):
                 ('rule', C.c_int32), ('counts', C.c_void_p)]
 
 
-RULE_SPARC, RULE_SEGMENTED = 0, 1
+RULE_SPARC, RULE_SEGMENTED, RULE_RANDOM = 0, 1, 2   # RULE_RANDOM: amp_bamp_random_trials_run only
 
 
 class AmpSynthArgs(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('channel0', C.c_uint64), ('trial0', C.c_uint64),
                 ('sw', C.c_void_p), ('A', C.c_void_p), ('At', C.c_void_p),
-                ('Lh', C.c_int32), ('band_blocks', C.c_int32), ('noise_std', C.c_float), ('pad', C.c_int32),
+                ('Lh', C.c_int32), ('band_blocks', C.c_int32), ('noise_std', C.c_float), ('message', C.c_int32),
                 ('x', C.c_void_p), ('sym', C.c_void_p), ('idx', C.c_void_p), ('y', C.c_void_p),
                 ('noise', C.c_void_p)]
 
@@ -163,6 +163,9 @@ SIGNATURES = {
     # several channels per trial batch: trial e uses channel e // per_channel
     'amp_bamp_trials_ch_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I]),
     'amp_bamp_trials_ch_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _I, _P]),
+    'amp_bamp_random_trials_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I]),
+    'amp_bamp_random_trials_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _I,
+                                             _P]),
     'amp_scamp_trials_ch_workspace_bytes': (C.c_size_t, [_D, _I, _I, _I]),
     'amp_scamp_trials_ch_run': (C.c_int, [_D, _K, C.POINTER(AmpScampArgs), C.POINTER(AmpTrialsDecideArgs), _I, _I,
                                           _P]),

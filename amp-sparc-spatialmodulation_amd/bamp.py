@@ -148,12 +148,21 @@ class BAMPLayer(nn.Module):
 class BAMP(LazyResult, nn.Module):
     """``gemm``: the GEMM arithmetic (amp_sparc.h amp_bamp_args.gemm): nat.GEMM_AUTO (f32 MFMA),
     GEMM_F32, GEMM_X3 (bf16x3 tiles, 24-bit operands) or GEMM_H2 (fp16x2 tiles, 22-bit operands,
-    opt-in).  The arithmetic that ran is reported in ``self.L.arithmetic``."""
+    opt-in).  The arithmetic that ran is reported in ``self.L.arithmetic``.
+    ``random_trials`` (opt-in, generator_mode 'random' at config.B == 1 only, else ValueError):
+    ``forward_trials`` batches that mode's B = 1 forwards (amp_bamp_random_trials_run: the
+    element-wise denoiser, decided by Loss.random_decision per trial).  Without it ``forward_trials``
+    refuses the mode, as VAMP's and SCAMP's do."""
 
-    def __init__(self, config: Config, gemm: int = nat.GEMM_AUTO) -> None:
+    def __init__(self, config: Config, gemm: int = nat.GEMM_AUTO, random_trials: bool = False) -> None:
         super().__init__()
         self.config = config
         self.gemm = gemm
+        if random_trials and (config.mode != 'random' or config.B != 1):
+            raise ValueError(f"BAMP(random_trials=True) batches generator_mode 'random' at config.B == 1 "
+                             f"(mode {config.mode!r}, B = {config.B}): 'sparc' and 'segmented' trial batches "
+                             'need no keyword, and a B > 1 batch shares its exit (use forward)')
+        self.random_trials = bool(random_trials)
         self.E = config.Na / config.Nr                                    # bamp.py:102
         self.layers = nn.ModuleList([BAMPLayer(config, i) for i in range(config.N_Layers)])
         self.L = Loss(config)
@@ -198,10 +207,12 @@ class BAMP(LazyResult, nn.Module):
 
     def trials_workspace_bytes(self, trials: int, per_channel: int) -> int:
         """Workspace bytes of a forward_trials call of `trials` trials at `per_channel` per channel
-        (amp_bamp_trials_ch_workspace_bytes; 0: the call would be refused)."""
+        (amp_bamp_trials_ch_workspace_bytes, with random_trials amp_bamp_random_trials_workspace_bytes;
+        0: the call would be refused)."""
         d = self.config.dims()
-        return int(nat.lib().amp_bamp_trials_ch_workspace_bytes(C.byref(d), self.config.N_Layers, int(trials),
-                                                                int(per_channel)))
+        lib = nat.lib()
+        query = lib.amp_bamp_random_trials_workspace_bytes if self.random_trials else lib.amp_bamp_trials_ch_workspace_bytes
+        return int(query(C.byref(d), self.config.N_Layers, int(trials), int(per_channel)))
 
     def forward_trials(self, H, ys, SNR: float, xs, symbols, indices, per_channel: int | None = None) -> list:
         """E independent single-trial detections that share ONE channel H and one SNR, in one
@@ -216,8 +227,13 @@ class BAMP(LazyResult, nn.Module):
         together with per_channel = R; trial e then uses channel e // R (the last channel may hold
         fewer than R trials; R = 1 is a channel per trial), and each trial still equals its own
         forward() with its own channel.  ValueError unless G == ceil(E / R).  A single matrix
-        without per_channel is the one-channel call."""
-        E = self._trials_check(ys, xs, symbols, indices)
+        without per_channel is the one-channel call.
+        generator_mode 'random' (BAMP(config, random_trials=True) only; ValueError otherwise): the
+        same call runs amp_bamp_random_trials_run, each trial the B = 1 forward with the element-wise
+        denoiser (bamp.py:79-88) and the P0 / Ps prior forward passes, decided by
+        Loss.random_decision (loss.py:252-280)."""
+        rnd = self.random_trials
+        E = self._trials_check(ys, xs, symbols, indices, modes=('random',) if rnd else ('sparc', 'segmented'))
         multi = per_channel is not None or isinstance(H, (list, tuple))
         if multi:
             Hc, R, n, N = _channel_stack(H, E, per_channel, 'H')
@@ -232,7 +248,10 @@ class BAMP(LazyResult, nn.Module):
             y, x, sym, idx, res, host, dec = self._trials_inputs(ys, xs, symbols, indices, E, n, dev)
             d, cst = cfg.dims(), cfg.constellation()
             lib = nat.lib()
-            if multi:
+            if rnd:
+                dec.rule = nat.RULE_RANDOM
+                wsb = lib.amp_bamp_random_trials_workspace_bytes(C.byref(d), cfg.N_Layers, E, R if multi else E)
+            elif multi:
                 wsb = lib.amp_bamp_trials_ch_workspace_bytes(C.byref(d), cfg.N_Layers, E, R)
             else:
                 wsb = lib.amp_bamp_trials_workspace_bytes(C.byref(d), cfg.N_Layers, E)
@@ -245,14 +264,18 @@ class BAMP(LazyResult, nn.Module):
             a = nat.AmpBampArgs()
             a.H, a.y = nat.dptr(Hc, name='H'), nat.dptr(y, name='y')
             a.max_iter = cfg.N_Layers
-            a.denoiser = 0
+            a.denoiser = 1 if rnd else 0
             a.noise_var = float(self.E / SNR)                                  # bamp.py:124
             a.P0, a.Ps = float(np.float32(cfg.P0)), float(np.float32(cfg.Ps))
             a.gemm = self.gemm
             a.xmap, a.xmmse, a.var = nat.dptr(xmap), nat.dptr(xm), nat.dptr(var)
             a.status = nat.dptr(res)
             a.ws, a.ws_bytes = nat.dptr(ws), ws.numel()
-            if multi:
+            if rnd:
+                nat.check(lib.amp_bamp_random_trials_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E,
+                                                         R if multi else E, nat.stream_ptr(dev)),
+                          'amp_bamp_random_trials_run')
+            elif multi:
                 nat.check(lib.amp_bamp_trials_ch_run(C.byref(d), C.byref(cst), C.byref(a), C.byref(dec), E, R,
                                                      nat.stream_ptr(dev)), 'amp_bamp_trials_ch_run')
             else:

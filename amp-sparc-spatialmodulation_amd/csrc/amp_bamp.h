@@ -289,6 +289,69 @@ __device__ __forceinline__ BampDenoisePolicy bamp_policy(const BampK& P, int t, 
     return pol;
 }
 
+// BAMPLayer.random_denoiser (bamp.py:79-88) for one entry, in the reference's dtypes: G(0) in
+// float32 (r - 0 stays complex64), G(a_k) in float64 (complex64 - complex128), norm / exp / var
+// in float64 (the float32 prior scalars promoted), complex128 / float64 as a reciprocal multiply.
+// c64: torch.tensor(config.symbols), complex128 (bamp.py:37).
+// KK: the table size as a compile-time bound (points k >= c64.K skipped): the loop is unrolled so
+// the by-value kernel-argument table is only read at constant offsets (a runtime-indexed loop made
+// the compiler copy the whole table into scratch memory at every kernel entry: ~900 B per lane).
+template <int KK>
+__device__ __forceinline__ void bamp_bayes_elem(const BampK& P, const Const64& c64, float rr, float ri, float cov,
+                                                float& xr, float& xi, float& var) {
+    const float a0 = hypotf(rr, ri);
+    const float g0 = expf(-(a0 * a0) / cov);
+    const double cd = (double)cov;
+    double gs = 0.0, sr = 0.0, si = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < KK; ++k) {
+        if (k >= c64.K) break;
+        const double a = hypot((double)rr - c64.re[k], (double)ri - c64.im[k]);
+        const double g = exp(-(a * a) / cd);
+        const double ak = hypot(c64.re[k], c64.im[k]);
+        gs += g;
+        sr += c64.re[k] * g;
+        si += c64.im[k] * g;
+        s2 += (ak * ak) * g;
+    }
+    double norm = (double)(P.P0 * g0) + (double)P.Ps * gs;
+    if (norm == 0.0) norm = 1e-9;                                       // regularize_zero (bamp.py:90-92)
+    const double rn = 1.0 / norm;
+    const double er = ((double)P.Ps * sr) * rn, ei = ((double)P.Ps * si) * rn;
+    const double ae = hypot(er, ei);
+    xr = (float)er;
+    xi = (float)ei;
+    var = (float)(((double)P.Ps * s2) / norm - ae * ae);
+}
+
+// The element-wise denoiser (generator_mode 'random') over rows [rho0, rho0 + nrho) of the C tile
+// bamp_xmap left in `lds`: xmmse, this iteration's var, and into pa the sum of var and the allclose
+// count against the previous var (bamp.py:140).  There is no batch-global shift in random_denoiser:
+// the section statistics of pa stay neutral.  Element e = threadIdx.x + i AMP_WG of the
+// nrho x BN / 2 block: the launch engine calls it once for the tile's rows, the trial engine row by
+// row (a row's BN / 2 columns then go to the threads its own B = 1 forward gives them, so the row's
+// partial is folded in that forward's order).
+template <int BN, int KC, int KK>
+__device__ __forceinline__ void bamp_bayes_rows(const BampK& P, const Const64& c64, int t, const float* lds, int row0,
+                                                int col0, int rho0, int nrho, int ncols, PartAcc& pa) {
+    using C = GemmCfg<BN, KC>;
+    float* vn = bvar(P, t);
+    const float* vp = bvar(P, t + 1);
+    for (int e = threadIdx.x; e < nrho * (BN / 2); e += AMP_WG) {
+        const int rho = rho0 + e / (BN / 2), cc = e % (BN / 2);
+        if (2 * cc < ncols) {
+            const size_t o = (size_t)(row0 + rho) * P.N + col0 / 2 + cc;
+            const float2 v = *reinterpret_cast<const float2*>(lds + rho * C::LDC + 2 * cc);
+            float xr, xi, var;
+            bamp_bayes_elem<KK>(P, c64, v.x, v.y, P.cov[o], xr, xi, var);
+            *reinterpret_cast<float2*>(P.xm + 2 * o) = make_float2(xr, xi);
+            vn[o] = var;
+            pa.sumvar += (double)var;
+            pa.notclose += torch_close(var, vp[o]) ? 0u : 1u;     // bamp.py:140
+        }
+    }
+}
+
 // One section for the exact float64 fix-up (section_absmax_f64 / exact_section_f64), o0 its first
 // position in [B][N]: the loader (xmap and 1 / tau, tau = cov / 2) and the store (xmmse, var and the
 // allclose delta against the previous var, added to *dnc)

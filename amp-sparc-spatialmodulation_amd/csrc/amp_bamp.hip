@@ -36,41 +36,6 @@ static inline bool bamp_h2_shape(const amp_dims* d) {
     return d->N % 64 == 0 && d->n % 64 == 0;
 }
 
-// BAMPLayer.random_denoiser (bamp.py:79-88) for one entry, in the reference's dtypes: G(0) in
-// float32 (r - 0 stays complex64), G(a_k) in float64 (complex64 - complex128), norm / exp / var
-// in float64 (the float32 prior scalars promoted), complex128 / float64 as a reciprocal multiply.
-// c64: torch.tensor(config.symbols), complex128 (bamp.py:37).
-// KK: the table size as a compile-time bound (points k >= c64.K skipped): the loop is unrolled so
-// the by-value kernel-argument table is only read at constant offsets (a runtime-indexed loop made
-// the compiler copy the whole table into scratch memory at every kernel entry: ~900 B per lane).
-template <int KK>
-__device__ __forceinline__ void bamp_bayes_elem(const BampK& P, const Const64& c64, float rr, float ri, float cov,
-                                                float& xr, float& xi, float& var) {
-    const float a0 = hypotf(rr, ri);
-    const float g0 = expf(-(a0 * a0) / cov);
-    const double cd = (double)cov;
-    double gs = 0.0, sr = 0.0, si = 0.0, s2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < KK; ++k) {
-        if (k >= c64.K) break;
-        const double a = hypot((double)rr - c64.re[k], (double)ri - c64.im[k]);
-        const double g = exp(-(a * a) / cd);
-        const double ak = hypot(c64.re[k], c64.im[k]);
-        gs += g;
-        sr += c64.re[k] * g;
-        si += c64.im[k] * g;
-        s2 += (ak * ak) * g;
-    }
-    double norm = (double)(P.P0 * g0) + (double)P.Ps * gs;
-    if (norm == 0.0) norm = 1e-9;                                       // regularize_zero (bamp.py:90-92)
-    const double rn = 1.0 / norm;
-    const double er = ((double)P.Ps * sr) * rn, ei = ((double)P.Ps * si) * rn;
-    const double ae = hypot(er, ei);
-    xr = (float)er;
-    xi = (float)ei;
-    var = (float)(((double)P.Ps * s2) / norm - ae * ae);
-}
-
 struct BampWs {
     float *Wabs2, *WH, *Wabs2T, *WHH, *v, *z, *invu, *s, *cov, *var1;
     unsigned short* ap;
@@ -205,22 +170,7 @@ __global__ __launch_bounds__(AMP_WG) void bamp_kb2(BampK P, Const64 c64, int t) 
     const BampDenoisePolicy pol = bamp_policy<BN, KC>(P, t, lds, sit, row0, col0, ncols, 0);
     PartAcc pa;
     if (P.elementwise) {
-        // no batch-global shift in random_denoiser: the section statistics stay neutral
-        float* vn = bvar(P, t);
-        const float* vp = bvar(P, t + 1);
-        for (int e = threadIdx.x; e < GBM * (BN / 2); e += AMP_WG) {
-            const int rho = e / (BN / 2), cc = e % (BN / 2);
-            if (rho < nrows && 2 * cc < ncols) {
-                const size_t o = (size_t)(row0 + rho) * P.N + col0 / 2 + cc;
-                const float2 v = *reinterpret_cast<const float2*>(lds + rho * C::LDC + 2 * cc);
-                float xr, xi, var;
-                bamp_bayes_elem<KK>(P, c64, v.x, v.y, P.cov[o], xr, xi, var);
-                *reinterpret_cast<float2*>(P.xm + 2 * o) = make_float2(xr, xi);
-                vn[o] = var;
-                pa.sumvar += (double)var;
-                pa.notclose += torch_close(var, vp[o]) ? 0u : 1u;     // bamp.py:140
-            }
-        }
+        bamp_bayes_rows<BN, KC, KK>(P, c64, t, lds, row0, col0, 0, nrows, ncols, pa);   // amp_bamp.h
     } else {
         denoise_sections<true, KK>(pol, nrows * pol.spr, P.M, P.c, pa);
     }

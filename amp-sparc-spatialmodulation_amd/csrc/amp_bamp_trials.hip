@@ -18,6 +18,11 @@
 // (amp_trials.h: OneChannel where the call has one channel, TrialChannels for several), one host
 // function runs either, and the operators of all channels are packed in a number of launches that
 // does not depend on G; tbamp_r is per trial.
+// amp_bamp_random_trials_run: the same run for generator_mode 'random' (one channel or several): the
+// element-wise Bayes denoiser (BAMPLayer.random_denoiser, bamp.py:79-88) in tbamp_kb2, row by row,
+// through the device function the launch engine's bamp_kb2 calls (amp_bamp.h bamp_bayes_rows); no
+// max|xi| shift, so tbamp_r only reduces and settles the exit; decided by Loss.random_decision per
+// trial (amp_trials_decide.hip).  The two entries above refuse that denoiser and that rule.
 #include <algorithm>
 #include <mutex>
 
@@ -142,9 +147,11 @@ __global__ __launch_bounds__(AMP_WG) void tbamp_kb1(BampK P, BampTrials R, CH ch
 }
 
 // bamp_kb2, the denoiser row by row: each live row's own partial, in the slot its B = 1 forward
-// stores it to, from scratch past the C tile (later rows still read the tile and the 1 / tau tile)
+// stores it to, from scratch past the C tile (later rows still read the tile and the 1 / tau tile).
+// P.elementwise (amp_bamp_random_trials_run): the row's element-wise denoiser, bamp_kb2's call
+// (bamp_bayes_rows) on that one row, its BN / 2 columns on the threads of the row's B = 1 forward.
 template <int BN, int KK, int KC, class CH>
-__global__ __launch_bounds__(AMP_WG) void tbamp_kb2(BampK P, BampTrials R, CH ch, int t) {
+__global__ __launch_bounds__(AMP_WG) void tbamp_kb2(BampK P, BampTrials R, CH ch, Const64 c64, int t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int s_stop[GBM];
     using C = GemmCfg<BN, KC>;
@@ -159,16 +166,22 @@ __global__ __launch_bounds__(AMP_WG) void tbamp_kb2(BampK P, BampTrials R, CH ch
     const int nct = P.ncpB2 / BN, slot = seq_part_slot(tile.cb, nct);
     for (int rho = 0; rho < nrows; ++rho) {
         if (s_stop[rho]) continue;   // workgroup-uniform
-        const BampDenoisePolicy pol = bamp_policy<BN, KC>(P, t, lds, sit, row0, col0, ncols, rho);
         PartAcc pa;
-        denoise_sections<true, KK>(pol, pol.spr, P.M, P.c, pa);
+        if (P.elementwise) {
+            bamp_bayes_rows<BN, KC, KK>(P, c64, t, lds, row0, col0, rho, 1, ncols, pa);
+        } else {
+            const BampDenoisePolicy pol = bamp_policy<BN, KC>(P, t, lds, sit, row0, col0, ncols, rho);
+            denoise_sections<true, KK>(pol, pol.spr, P.M, P.c, pa);
+        }
         part_block_store(pa, P.parts + (size_t)(row0 + rho) * nct + slot, lds + C::CTILE_FLOATS);
     }
 }
 
 // Workgroup e: trial e's reduction, exact float64 fix-up against its own max|xi| and allclose
 // decision (bamp.py:140) — bamp_r + bamp_fixall of amp_bamp.hip on the trial's rows, every trial in
-// parallel.
+// parallel.  The element-wise denoiser has no max|xi| shift and leaves the section statistics of its
+// partials neutral (maxabs 0, minsecmax +inf): neither the all-NaN fill nor the fix-up is entered, the
+// workgroup reduces the partials and settles stopped, T, the status record and the stop counter.
 __global__ __launch_bounds__(TBRWG) void tbamp_r(BampK P, BampTrials R, Const64 c64, int t) {
     __shared__ __attribute__((aligned(16))) float lds[512];
     __shared__ double s_fix[TBRWG / 64];
@@ -180,7 +193,9 @@ __global__ __launch_bounds__(TBRWG) void tbamp_r(BampK P, BampTrials R, Const64 
     PartAcc pa = part_reduce_all(P.parts + (size_t)e * nct, nct, lds);
     uint32_t notclose = pa.notclose;
     int fixed = 0;
-    if (part_allnan(pa)) {
+    if (P.elementwise) {
+        // nothing to settle but the allclose count
+    } else if (part_allnan(pa)) {
         if (!cur.fixed_all) nan_fill(P.xm + (size_t)e * 2 * P.N, bvar(P, t) + (size_t)e * P.N, (size_t)P.N);
         notclose = 1u;
         fixed = -1;
@@ -241,23 +256,27 @@ static int tbamp_attrs() {
 }
 
 template <int KK, class CH>
-static void tbamp_launch_kb2(const BampK& P, const BampTrials& R, const CH& ch, int gr, int t, hipStream_t st) {
+static void tbamp_launch_kb2(const BampK& P, const BampTrials& R, const CH& ch, const Const64& c64, int gr, int t,
+                             hipStream_t st) {
     if (P.bn == 128)
-        hipLaunchKernelGGL((tbamp_kb2<128, KK, 256, CH>), dim3(gr, P.ncpB2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
+        hipLaunchKernelGGL((tbamp_kb2<128, KK, 256, CH>), dim3(gr, P.ncpB2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch,
+                           c64, t);
     else
-        hipLaunchKernelGGL((tbamp_kb2<256, KK, GKC, CH>), dim3(gr, P.ncpB2 / 256), dim3(AMP_WG), TB_LDS_W, st, P, R, ch, t);
+        hipLaunchKernelGGL((tbamp_kb2<256, KK, GKC, CH>), dim3(gr, P.ncpB2 / 256), dim3(AMP_WG), TB_LDS_W, st, P, R, ch,
+                           c64, t);
 }
 
 // iteration t's four GEMM launches over gr row tiles
 template <class CH>
-static void tbamp_launch_gemms(const BampK& P, const BampTrials& R, const CH& ch, int gr, int t, hipStream_t st) {
+static void tbamp_launch_gemms(const BampK& P, const BampTrials& R, const CH& ch, const Const64& c64, int gr, int t,
+                               hipStream_t st) {
     if (P.N % 4 != 0)
         hipLaunchKernelGGL((tbamp_ka1<ALoadPair, CH>), dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
     else
         hipLaunchKernelGGL((tbamp_ka1<ALoadPlain, CH>), dim3(gr, P.ncpA1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
     hipLaunchKernelGGL(tbamp_ka2<CH>, dim3(gr, P.ncpA2 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
     hipLaunchKernelGGL(tbamp_kb1<CH>, dim3(gr, P.ncpB1 / 128), dim3(AMP_WG), TB_LDS_S, st, P, R, ch, t);
-    dispatch_K(P.c.K, [&](auto kk) { tbamp_launch_kb2<decltype(kk)::value>(P, R, ch, gr, t, st); });
+    dispatch_K(P.c.K, [&](auto kk) { tbamp_launch_kb2<decltype(kk)::value>(P, R, ch, c64, gr, t, st); });
 }
 
 // The operators of G channels (H: c64 [G][n][N]) and their band ranges, each channel's own, in a
@@ -280,10 +299,13 @@ static int tbamp_pack_ch(const BampK& P, const TrialChannels& CH, const float2* 
     return AMP_OK;
 }
 
-// Both entries.  fn: the entry that was called (amp_bamp_trials_run passes per_channel = trials: one
-// channel); a->H holds the G = ceil(trials / per_channel) channels in order.
+// Every entry.  fn: the entry that was called (amp_bamp_trials_run passes per_channel = trials: one
+// channel); a->H holds the G = ceil(trials / per_channel) channels in order.  random
+// (amp_bamp_random_trials_run): the element-wise denoiser (a->denoiser == 1, the prior a->P0 / a->Ps)
+// and the 'random' decision rule; the other entries refuse both.
 static int tbamp_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
-                     const amp_trials_decide_args* dec, int trials, int per_channel, const char* fn, hipStream_t st) {
+                     const amp_trials_decide_args* dec, int trials, int per_channel, const char* fn, hipStream_t st,
+                     bool random = false) {
     int rc = check_dims(d, c, true, true);   // any n, any even N, a partial last column tile (amp_bamp_run)
     if (rc) return rc;
     AMP_REQUIRE(d->B == 1, "%s: dims describe ONE trial (B = %d, must be 1)", fn, d->B);
@@ -294,21 +316,29 @@ static int tbamp_run(const amp_dims* d, const amp_constellation* c, const amp_ba
     AMP_REQUIRE(a && a->H && a->y && a->xmap && a->xmmse && a->var && a->status && a->ws, "%s: null pointer argument",
                 fn);
     AMP_REQUIRE(a->max_iter > 0, "%s: max_iter must be positive", fn);
-    AMP_REQUIRE(a->denoiser == 0, "%s: the element-wise denoiser ('random' mode) has no independent-trial form", fn);
+    if (random)
+        AMP_REQUIRE(a->denoiser == 1, "%s: denoiser %d (this entry runs the element-wise denoiser, 1)", fn, a->denoiser);
+    else
+        AMP_REQUIRE(a->denoiser == 0, "%s: the element-wise denoiser ('random' mode) has no independent-trial form", fn);
     AMP_REQUIRE(a->gemm == AMP_GEMM_AUTO || a->gemm == AMP_GEMM_F32, "%s: f32 GEMMs only (gemm %d)", fn, a->gemm);
     const int E = trials;
     int per = per_channel;
     const int G = trial_channels(E, per);
     AMP_REQUIRE(G <= WCH_MAX, "%s: %d channels (at most %d per call: a grid axis)", fn, G, WCH_MAX);
+    TrialsDecide td{};
+    // the 'random' rule's own limits (Na <= 64) before the workspace is looked at
+    if (random && dec && (rc = trials_decide_args(d, dec, a->xmap, a->xmmse, td, true))) return rc;
     const TBampWs w = tbamp_carve(d, E, a->ws, G);
     AMP_REQUIRE(a->ws_bytes >= w.bytes, "%s: workspace %zu < %zu bytes", fn, a->ws_bytes, w.bytes);
-    TrialsDecide td{};
-    if (dec && (rc = trials_decide_args(d, dec, a->xmap, a->xmmse, td))) return rc;
+    if (!random && dec && (rc = trials_decide_args(d, dec, a->xmap, a->xmmse, td))) return rc;
     if ((rc = tbamp_attrs())) return rc;
-    BampK P{};             // f32 tiles, the block denoiser (h2 = x3 = elementwise = 0)
+    BampK P{};             // f32 tiles (h2 = x3 = 0); the block denoiser unless `random`
     bamp_geometry(d, E, P);
     P.max_iter = a->max_iter;
     P.sigma2 = (float)a->noise_var;
+    P.elementwise = random ? 1 : 0;
+    P.P0 = a->P0;
+    P.Ps = a->Ps;
     P.Wabs2 = w.Wabs2; P.WH = w.WH; P.Wabs2T = w.Wabs2T; P.WHH = w.WHH;   // channel 0's; the GEMM kernels step to theirs
     P.y = (const float*)a->y; P.v = w.v; P.z = w.z; P.invu = w.invu; P.s = w.s; P.cov = w.cov;
     P.xmap = (float*)a->xmap; P.xm = (float*)a->xmmse; P.var0 = (float*)a->var; P.var1 = w.var1;
@@ -334,9 +364,9 @@ static int tbamp_run(const amp_dims* d, const amp_constellation* c, const amp_ba
     const int gr = G * CH.tpg;                     // <= E row tiles; one channel: cdiv(E, 32)
     for (int t = 0; t < P.max_iter; ++t) {
         if (G == 1)
-            tbamp_launch_gemms(P, R, OneChannel{}, gr, t, st);
+            tbamp_launch_gemms(P, R, OneChannel{}, c64, gr, t, st);
         else
-            tbamp_launch_gemms(P, R, CH, gr, t, st);
+            tbamp_launch_gemms(P, R, CH, c64, gr, t, st);
         hipLaunchKernelGGL(tbamp_r, dim3(E), dim3(TBRWG), 0, st, P, R, c64, t);
         AMP_LAUNCH_CHECK("tbamp iteration");
     }
@@ -373,6 +403,16 @@ size_t amp_bamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, i
 int amp_bamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
                            const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
     return tbamp_run(d, c, a, dec, trials, per_channel, "amp_bamp_trials_ch_run", (hipStream_t)stream);
+}
+
+// the carve is amp_bamp_trials_ch_run's (the decision's workspace holds either rule's partials)
+size_t amp_bamp_random_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel) {
+    return amp_bamp_trials_ch_workspace_bytes(d, max_iter, trials, per_channel);
+}
+
+int amp_bamp_random_trials_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
+                               const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream) {
+    return tbamp_run(d, c, a, dec, trials, per_channel, "amp_bamp_random_trials_run", (hipStream_t)stream, true);
 }
 
 }  // extern "C"

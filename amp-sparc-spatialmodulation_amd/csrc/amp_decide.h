@@ -341,6 +341,118 @@ __device__ __forceinline__ void count_section(const DecConst& c, long long s, in
     if (lin == Lin - 1) q.mseL += se;
 }
 
+// Random decision (Loss.random_decision, loss.py:252-280; generator_mode='random') of one channel
+// use by one thread: of the row's Nt entries the Na largest |x_m| (np.argsort()[-Na:]: NaN largest;
+// exact ties in an implementation-defined order in numpy, by larger index here), each decided to
+// its nearest point (float64, first minimum); the decided positions in ascending order are
+// compared with the true sorted indices / labels of that row (loss.py:165-178).
+__device__ __forceinline__ bool rnd_greater(bool n1, float v1, int m1, bool n2, float v2, int m2) {
+    if (n1 != n2) return n1;
+    if (n1) return m1 > m2;
+    if (v1 != v2) return v1 > v2;
+    return m1 > m2;
+}
+
+constexpr int AMP_DEC_MAX_NA = 64;
+
+// Channel use `row` (lin = row % Lin) of rows that start at xmap / x / xmmse ([rows][Nt]), sym / idx
+// ([rows][Na]; the flat indices count from the first of these rows).  dec (optional): [rows][Na]
+// position * K + k.  mrow: the channel use's Na mismatch bytes in the layout map_count_kernel /
+// trials_count_kernel fold (one flag, then zeros).  Adds the row's counters to q.
+template <int KK>
+__device__ __forceinline__ void random_decide_row(const DecConst& c, int Nt, int Na, int Lin, int row,
+                                                  const float2* xmap, const float2* x, const float2* xmmse,
+                                                  const long long* sym, const long long* idx, long long ibmask, int* dec,
+                                                  unsigned char* mrow, DecPart& q) {
+    constexpr int K = KK;
+    constexpr int KU = KUnroll<KK>::value;
+    const long long sbmask = (1LL << c.sbits) - 1;
+    const float2* xm = xmap + (size_t)row * Nt;
+    const float2* xt = x + (size_t)row * Nt;
+    const float2* xe = xmmse + (size_t)row * Nt;
+    int pos[AMP_DEC_MAX_NA];
+    bool pn = true;
+    float pv = 0.f;
+    int pm = 0x7fffffff;
+    for (int a = 0; a < Na; ++a) {
+        bool bn = false;
+        float bv = -1.f;
+        int bm = -1;
+        for (int m = 0; m < Nt; ++m) {
+            const float v = hypotf(xm[m].x, xm[m].y);
+            const bool vn = v != v;
+            if (!rnd_greater(pn, pv, pm, vn, v, m)) continue;     // already chosen
+            if (bm < 0 || rnd_greater(vn, v, m, bn, bv, bm)) { bn = vn; bv = v; bm = m; }
+        }
+        pos[a] = bm;
+        pn = bn; pv = bv; pm = bm;
+    }
+    for (int a = 1; a < Na; ++a)                                   // ascending positions
+        for (int j = a; j > 0 && pos[j - 1] > pos[j]; --j) { const int t = pos[j]; pos[j] = pos[j - 1]; pos[j - 1] = t; }
+    const int lin = row % Lin;
+    int mism = 0;
+    double se = 0.0;
+    for (int j = 0; j < Na; ++j) {
+        const int m = pos[j];
+        const double xr = (double)xm[m].x, xi = (double)xm[m].y;
+        double d = INFINITY;
+        int kh = 0;
+#pragma unroll KU
+        for (int k = 0; k < K; ++k) {
+            const double ds = hypot(xr - c.re[k], xi - c.im[k]);
+            if (ds < d) { d = ds; kh = k; }
+        }
+        pos[j] = m * K + kh;
+        const long long e = (long long)row * Na + j;
+        const long long ih = (long long)row * Nt + m;
+        long long sh = 0;
+#pragma unroll KU
+        for (int k = 0; k < K; ++k)
+            if (k == kh) sh = c.gray[k];
+        q.ier += (ih != idx[e]);
+        q.ser += (sh != sym[e]);
+        q.iber += __popcll((unsigned long long)((ih ^ idx[e]) & ibmask));
+        q.sber += __popcll((unsigned long long)((sh ^ sym[e]) & sbmask));
+        if (dec) dec[e] = pos[j];
+    }
+    for (int m = 0; m < Nt; ++m) {
+        float hr = 0.f, hi = 0.f;
+        for (int j = 0; j < Na; ++j)
+            if (pos[j] / K == m) {
+                const int kh = pos[j] - m * K;
+#pragma unroll KU
+                for (int k = 0; k < K; ++k)
+                    if (k == kh) { hr = c.re32[k]; hi = c.im32[k]; }
+            }
+        mism |= (hr - xt[m].x != 0.f || hi - xt[m].y != 0.f) ? 1 : 0;
+        const float dr = xe[m].x - xt[m].x, di = xe[m].y - xt[m].y;
+        se += (double)dr * dr + (double)di * di;
+    }
+    for (int a = 0; a < Na; ++a) mrow[a] = (a == 0) ? (unsigned char)mism : 0;
+    q.mse += se;
+    if (lin == 0) q.msef += se;
+    if (lin == Lin / 2) q.msem += se;
+    if (lin == Lin - 1) q.mseL += se;
+}
+
+// The workgroup's DecPart (every thread's q) in the fixed order of the random decision's kernels:
+// lane trees, then the waves in order.  Thread 0 stores it to *out.
+__device__ __forceinline__ void random_part_store(DecPart q, DecPart* out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    q.ier = group_sum(q.ier, 64); q.ser = group_sum(q.ser, 64); q.iber = group_sum(q.iber, 64);
+    q.sber = group_sum(q.sber, 64);
+    q.mse = group_sum(q.mse, 64); q.msef = group_sum(q.msef, 64); q.msem = group_sum(q.msem, 64);
+    q.mseL = group_sum(q.mseL, 64);
+    __shared__ DecPart sp[AMP_WG / 64];
+    if (lane == 0) sp[wave] = q;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        DecPart o = sp[0];
+        for (int w = 1; w < AMP_WG / 64; ++w) decpart_add(o, sp[w]);
+        *out = o;
+    }
+}
+
 __host__ inline DecConst to_decconst(const amp_constellation* c) {
     DecConst d;
     d.K = c->K;

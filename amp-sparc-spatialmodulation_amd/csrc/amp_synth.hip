@@ -5,7 +5,8 @@
 // Random numbers are Philox4x32-10 (Salmon et al., SC'11; the Random123 constants) written out
 // here: key = (seed low, seed high), counter = (index, id low, id high, stream), so a draw is a
 // pure function of (seed, stream, id, index) and no state is kept anywhere.  Stream 0: channel
-// taps (id = channel, index = (r Nt + t) Lh + l), 1: message (id = trial, index = section),
+// taps (id = channel, index = (r Nt + t) Lh + l), 1: message (id = trial, index = section; message = 1:
+// index = u Na + j, draw j of channel use u),
 // 2: noise (id = trial, index = row).
 #include "amp_host.h"
 
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(256) void synth_channels_kernel(SynthChK P) {
 }
 
 struct SynthTrK {
-    int n, N, L, M, K, Na, Nr, Lin, band, per, nb;
+    int n, N, L, M, K, Na, Nr, Nt, Lin, band, per, nb, message;
     uint2 key;
     unsigned long long id0;
     float noise_std;
@@ -112,6 +113,11 @@ constexpr int SYNTH_ROWS = 256;   // rows of y per workgroup, one per lane
 // another and nothing is accumulated with atomics.  Lane = row: every read of At is one contiguous
 // run of a column's row of At.  KK: the constellation size (the table is read with constant indices
 // from the kernel arguments).
+// P.message = 1 (Data.random, data.py:55-72): the list holds, per channel use u, its Na active
+// columns in ascending order with one symbol for all of them; ONE lane builds a channel use's subset
+// (Floyd's sampling, amp_sparc.h; the chosen antennas kept sorted in the list itself), once per
+// workgroup and not per output row.  Entries [u Na, (u + 1) Na) lie in column block u, as sections
+// do, so the band ranges and the accumulation below are the same code for both messages.
 template <int KK>
 __global__ __launch_bounds__(SYNTH_ROWS) void synth_trials_kernel(SynthTrK P) {
     extern __shared__ float2 synth_lds[];
@@ -120,6 +126,37 @@ __global__ __launch_bounds__(SYNTH_ROWS) void synth_trials_kernel(SynthTrK P) {
     const int tid = threadIdx.x;
     const int e = blockIdx.x / P.nb, b = blockIdx.x - e * P.nb;
     const unsigned long long id = P.id0 + (unsigned)e;
+    if (P.message == 1) {
+        for (int u = tid; u < P.Lin; u += SYNTH_ROWS) {
+            int* sub = scol + u * P.Na;                 // the antennas chosen so far, ascending
+            int k = 0;
+            for (int j = 0; j < P.Na; ++j) {
+                const uint4 w = synth_draw(P.key, id, SYNTH_MESSAGE, (unsigned)(u * P.Na + j));
+                if (j == 0) k = (int)__umulhi(w.y, (unsigned)P.K);
+                const int J = P.Nt - P.Na + j;
+                int t = (int)__umulhi(w.x, (unsigned)(J + 1));
+                for (int i = 0; i < j; ++i)
+                    if (sub[i] == t) { t = J; break; }  // J itself is never in the list yet: every entry is < J
+                int i = j;
+                for (; i > 0 && sub[i - 1] > t; --i) sub[i] = sub[i - 1];
+                sub[i] = t;
+            }
+            float vr = 0.f, vi = 0.f;
+            int gr = 0;
+#pragma unroll
+            for (int q = 0; q < KK; ++q)
+                if (q == k) { vr = P.re[q]; vi = P.im[q]; gr = P.gray[q]; }
+            for (int j = 0; j < P.Na; ++j) {
+                const int s = u * P.Na + j, col = u * P.Nt + sub[j];
+                sval[s] = make_float2(vr, vi);
+                sub[j] = col;
+                if (b == 0) {
+                    P.sym[(size_t)e * P.L + s] = gr;
+                    P.idx[(size_t)e * P.L + s] = col;
+                }
+            }
+        }
+    } else
     for (int s = tid; s < P.L; s += SYNTH_ROWS) {
         const uint4 w = synth_draw(P.key, id, SYNTH_MESSAGE, (unsigned)s);
         const int pos = (int)__umulhi(w.x, (unsigned)P.M), k = (int)__umulhi(w.y, (unsigned)P.K);
@@ -142,6 +179,15 @@ __global__ __launch_bounds__(SYNTH_ROWS) void synth_trials_kernel(SynthTrK P) {
         const int c1 = min(P.N, (b + 1) * chunk);
         const int sh = __ffs(P.M) - 1;          // M is a power of two
         float2* __restrict__ x = P.x + (size_t)e * P.N;
+        if (P.message == 1) {
+            for (int c = b * chunk + tid; c < c1; c += SYNTH_ROWS) {
+                const int s0 = (c / P.Nt) * P.Na;       // the channel use's Na entries
+                float2 v = make_float2(0.f, 0.f);
+                for (int j = 0; j < P.Na; ++j)
+                    if (scol[s0 + j] == c) v = sval[s0 + j];
+                x[c] = v;
+            }
+        } else
         for (int c = b * chunk + tid; c < c1; c += SYNTH_ROWS) {
             const int s = c >> sh;
             x[c] = scol[s] == c ? sval[s] : make_float2(0.f, 0.f);
@@ -235,13 +281,15 @@ int amp_synth_trials(const amp_dims* d, const amp_constellation* c, const amp_sy
     AMP_REQUIRE(cdiv(trials, per_channel) <= WCH_MAX, "amp_synth_trials: more than %d channels", WCH_MAX);
     AMP_REQUIRE(a->band_blocks >= 0 && a->band_blocks <= d->Lout, "amp_synth_trials: band_blocks = %d outside [0, Lout = %d]",
                 a->band_blocks, d->Lout);
+    AMP_REQUIRE(a->message == 0 || a->message == 1, "amp_synth_trials: message = %d (0: one point per section, 1: Na "
+                "antennas per channel use)", a->message);
     AMP_REQUIRE(d->L <= SYNTH_MAX_L, "amp_synth_trials: L = Na Lin = %d sections beyond %d (the section list lives in LDS)",
                 d->L, SYNTH_MAX_L);
     const int nb = cdiv(d->n, SYNTH_ROWS);
     AMP_REQUIRE((long long)trials * nb <= 0x7fffffffLL, "amp_synth_trials: trials x row tiles beyond the grid");
     SynthTrK P;
-    P.n = d->n; P.N = d->N; P.L = d->L; P.M = d->M; P.K = c->K; P.Na = d->Na; P.Nr = d->Nr; P.Lin = d->Lin;
-    P.band = a->band_blocks; P.per = per_channel; P.nb = nb;
+    P.n = d->n; P.N = d->N; P.L = d->L; P.M = d->M; P.K = c->K; P.Na = d->Na; P.Nr = d->Nr; P.Nt = d->Nt; P.Lin = d->Lin;
+    P.band = a->band_blocks; P.per = per_channel; P.nb = nb; P.message = a->message;
     P.key = make_uint2((unsigned)a->seed, (unsigned)(a->seed >> 32));
     P.id0 = a->trial0;
     P.noise_std = a->noise_std;

@@ -135,7 +135,9 @@ inline void dispatch_K(int K, const F& f) {
 
 // Per-trial decision + counters (amp_trials_decide.hip): Loss at B = 1 for each of `trials` rows
 // (loss.py:67-179 with Ns = Lin Na, flat indices local to the trial), rule 0 MAP (sparc,
-// loss.py:282-302) or 1 segmented (loss.py:222-250).  ws: trials_decide_ws_bytes.
+// loss.py:282-302), 1 segmented (loss.py:222-250) or 2 random (loss.py:252-280: per channel use the
+// Na largest |x_m|; trials_decide_args takes it with random_entry only, amp_bamp_random_trials_run's
+// call, and refuses it for every other entry).  ws: trials_decide_ws_bytes.
 struct TrialsDecide {
     const float2* xmap;
     const float2* xmmse;
@@ -149,6 +151,6 @@ size_t trials_decide_ws_bytes(const amp_dims* d, int trials);
 int trials_decide_launch(const amp_dims* d, const amp_constellation* c, const TrialsDecide& a, int trials, void* ws,
                          hipStream_t st);
 int trials_decide_args(const amp_dims* d, const amp_trials_decide_args* dec, const void* xmap, const void* xmmse,
-                       TrialsDecide& out);
+                       TrialsDecide& out, bool random_entry = false);
 
 }  // namespace amp

@@ -7,6 +7,8 @@
 // The kernels are map_decide_kernel / map_count_kernel (amp_decide.hip) with the trial as
 // blockIdx.y: each trial's sections go to the same workgroups, lane groups and partial slots as in
 // its own B = 1 call, so its counters and float64 sums are the same bits.
+// amp_bamp_random_trials_run alone also decides by random_decision (loss.py:252-280, AMP_RULE_RANDOM):
+// random_decide_kernel's row function (amp_decide.h) with the trial as blockIdx.y.
 #include <algorithm>
 
 #include "amp_trials.h"
@@ -69,6 +71,22 @@ __global__ __launch_bounds__(AMP_WG) void trials_decide_kernel(TDecK P) {
         }
         P.parts[(size_t)blockIdx.y * P.nblk + blockIdx.x] = o;
     }
+}
+
+// The 'random' rule (Loss.random_decision, loss.py:252-280) per trial: random_decide_kernel
+// (amp_decide.hip) with the trial as blockIdx.y.  Trial e's Lin channel uses go to the threads and
+// partial slots of its own B = 1 call (row = its local channel use; sym / idx / the flat indices local
+// to the trial), so its counters and float64 sums are the same bits.
+template <int KK>
+__global__ __launch_bounds__(AMP_WG) void trials_random_decide_kernel(TDecK P, int Nt) {
+    const size_t e = blockIdx.y;
+    DecPart q = decpart_zero();
+    const long long ibmask = dec_ibmask(P.ibits);
+    const size_t o = e * (size_t)P.Lin * Nt;
+    for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < P.Lin; row += gridDim.x * blockDim.x)
+        random_decide_row<KK>(P.c, Nt, P.Na, P.Lin, row, P.xmap + o, P.x + o, P.xmmse + o, P.sym + e * P.L,
+                              P.idx + e * P.L, ibmask, nullptr, P.mism + e * P.L + (size_t)row * P.Na, q);
+    random_part_store(q, P.parts + e * P.nblk + blockIdx.x);
 }
 
 // workgroup e: trial e's channel-use / trial "any mismatch" counts (loss.py:133-136, 150) and its
@@ -153,9 +171,15 @@ size_t trials_decide_ws_bytes(const amp_dims* d, int trials) {
 }
 
 int trials_decide_args(const amp_dims* d, const amp_trials_decide_args* dec, const void* xmap, const void* xmmse,
-                       TrialsDecide& out) {
+                       TrialsDecide& out, bool random_entry) {
     AMP_REQUIRE(dec->x && dec->sym && dec->idx && dec->counts, "amp_trials_decide_args: null pointer argument");
-    AMP_REQUIRE(dec->rule == AMP_RULE_SPARC || dec->rule == AMP_RULE_SEGMENTED,
+    if (random_entry) {
+        AMP_REQUIRE(dec->rule == AMP_RULE_RANDOM, "amp_trials_decide_args: rule %d (amp_bamp_random_trials_run decides by "
+                    "AMP_RULE_RANDOM)", dec->rule);
+        AMP_REQUIRE(d->Na >= 1 && d->Na <= AMP_DEC_MAX_NA && d->Na <= d->Nt,
+                    "amp_trials_decide_args: the 'random' rule takes Na <= %d (Na = %d)", AMP_DEC_MAX_NA, d->Na);
+    }
+    AMP_REQUIRE(random_entry || dec->rule == AMP_RULE_SPARC || dec->rule == AMP_RULE_SEGMENTED,
                 "amp_trials_decide_args: rule %d (the 'random' rule has no independent-trial form)", dec->rule);
     AMP_REQUIRE(dec->ibits_trunc >= 0 && dec->ibits_trunc < 64, "amp_trials_decide_args: ibits_trunc out of range");
     AMP_REQUIRE(d->Lin * d->Na * d->M == d->N, "amp_trials_decide_args: inconsistent dims");
@@ -179,6 +203,23 @@ int trials_decide_launch(const amp_dims* d, const amp_constellation* c, const Tr
     P.parts = cv.take<DecPart>((size_t)trials * P.nblk);
     P.out = a.counts;
     P.c = to_decconst(c);
+    if (P.rule == AMP_RULE_RANDOM) {
+        // amp_random_decide_count's grid at B = 1, per trial (its partials fit the carve above)
+        P.nblk = std::max(1, std::min(cdiv(d->Lin, AMP_WG), P.nblk));
+        const dim3 g(P.nblk, trials), b(AMP_WG);
+        switch (P.c.K) {
+        case 1: hipLaunchKernelGGL(trials_random_decide_kernel<1>, g, b, 0, st, P, d->Nt); break;
+        case 2: hipLaunchKernelGGL(trials_random_decide_kernel<2>, g, b, 0, st, P, d->Nt); break;
+        case 4: hipLaunchKernelGGL(trials_random_decide_kernel<4>, g, b, 0, st, P, d->Nt); break;
+        case 8: hipLaunchKernelGGL(trials_random_decide_kernel<8>, g, b, 0, st, P, d->Nt); break;
+        case 16: hipLaunchKernelGGL(trials_random_decide_kernel<16>, g, b, 0, st, P, d->Nt); break;
+        default: hipLaunchKernelGGL(trials_random_decide_kernel<64>, g, b, 0, st, P, d->Nt); break;
+        }
+        AMP_LAUNCH_CHECK("trials_random_decide");
+        hipLaunchKernelGGL(trials_count_kernel, dim3(trials), dim3(1024), 0, st, P);
+        AMP_LAUNCH_CHECK("trials_count");
+        return AMP_OK;
+    }
     switch (P.c.K) {
     case 1: trials_launch_decide_k<1>(P, trials, st); break;
     case 2: trials_launch_decide_k<2>(P, trials, st); break;

@@ -27,13 +27,13 @@ from loss import Loss
 _DIRS = {'vamp': 'VAMP', 'bamp': 'BAMPfinal', 'scamp': 'SCAMP'}   # vamp_model.py:29 etc.
 
 
-def _detector(name: str, config: Config):
+def _detector(name: str, config: Config, random_trials: bool = False):
     if name == 'vamp':
         from vamp import VAMP
         return VAMP(config)
     if name == 'bamp':
         from bamp import BAMP
-        return BAMP(config)
+        return BAMP(config, random_trials=True) if random_trials else BAMP(config)
     if name == 'scamp':
         from scamp import SCAMP
         return SCAMP(config)
@@ -101,7 +101,10 @@ class Model(nn.Module):
         `res` epochs per channel (vamp_model.py:91, 98) — with the runs of epochs that share a
         channel detected as independent trials in one launch sequence (forward_trials), in chunks
         of at most group_trials; every trial keeps its own scalars, shift and exit, so the sweep
-        equals the per-epoch loop.  res = 1 degenerates to single forward calls.
+        equals the per-epoch loop.  res = 1 degenerates to single forward calls.  generator_mode
+        'random' (BAMP only): the detector is built with random_trials=True and goes through the same
+        grouping; parity mode keeps drawing Data.random in the reference's call order, throughput mode
+        needs synth_trials (TrialSynth draws that message; Data has no device generator for it).
         trial_channels (> 0, with group_trials = n, VAMP / BAMP / SCAMP; opt-in): one forward_trials call
         may hold the trials of up to trial_channels whole `res` blocks, each with its own channel, and at
         most n trials (forward_trials(..., per_channel=res): amp_vamp_trials_ch_run /
@@ -146,7 +149,9 @@ class Model(nn.Module):
             else:
                 from scamp import ShardedSCAMP
                 amp = ShardedSCAMP(config)
-        self.amp = amp if amp is not None else _detector(detector, config)
+        # generator_mode 'random' is batched by BAMP(random_trials=True) alone (a detector passed in is used as given)
+        rnd = bool(group_trials) and group_trials > 0 and detector == 'bamp' and config.mode == 'random' and config.B == 1
+        self.amp = amp if amp is not None else _detector(detector, config, random_trials=rnd)
         self.loss = Loss(config)
         self.rng = rng
         self.channel = Channel(config, rng=rng)

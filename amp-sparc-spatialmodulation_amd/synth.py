@@ -4,10 +4,12 @@ and all E trials' x / sym / idx / noise / y in one launch (amp_synth_trials), in
 ``Channel.generate_as_sparc`` per channel and one ``Data.generate_message`` + ``Channel.awgn`` +
 dense ``A x`` per trial.
 
-Same distributions as the reference's generators (channel.py:75-95, data.py:74-91,
-channel.py:103-116), its own random stream: Philox4x32-10, every draw a pure function of
+Same distributions as the reference's generators (channel.py:75-95, data.py:74-91 or, for
+generator_mode 'random', data.py:55-72: an exactly uniform Na-subset of the Nt antennas per channel
+use and one symbol for all of them, amp_synth_args.message = 1; channel.py:103-116), its own random stream: Philox4x32-10, every draw a pure function of
 (seed, stream, id, index) (include/amp_sparc.h), so a trial's inputs do not depend on how the
-trials are grouped into calls.  tests/synth_ref.py restates the mapping in numpy.
+trials are grouped into calls.  tests/synth_ref.py restates the mapping in numpy
+(tests/synth_random_ref.py the 'random' message).
 """
 from __future__ import annotations
 
@@ -23,9 +25,6 @@ from config import Config
 
 class TrialSynth:
     def __init__(self, config: Config, seed: int) -> None:
-        if config.mode not in ('sparc', 'segmented'):
-            raise ValueError(f"TrialSynth: generator_mode {config.mode!r} has no independent-trial form "
-                             "('sparc' and 'segmented' only)")
         if not config.is_complex:
             raise ValueError('TrialSynth: the trial engines take complex64 inputs (is_complex=True)')
         self.config = config
@@ -93,6 +92,7 @@ class TrialSynth:
             a.At = nat.dptr(At, torch.complex64, 'At')
             a.band_blocks = cfg.Lh if band else 0
             a.noise_std = float(np.sqrt(cfg.Na / cfg.Nr / SNR / 2))          # channel.py:153
+            a.message = 1 if cfg.mode == 'random' else 0                     # Data.random / Data.segmented
             a.x, a.sym, a.idx, a.y = nat.dptr(x), nat.dptr(sym), nat.dptr(idx), nat.dptr(y)
             a.noise = nat.dptr(noise) if want_noise else None
             cst = cfg.constellation()

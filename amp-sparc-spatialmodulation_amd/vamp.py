@@ -344,14 +344,15 @@ class LazyResult:
     _trials_ring = None
     _trials_i = 1
 
-    def _trials_check(self, ys, xs, symbols, indices) -> int:
+    def _trials_check(self, ys, xs, symbols, indices, modes=('sparc', 'segmented')) -> int:
+        """modes: the generator modes this detector batches ('random': BAMP(random_trials=True) alone)."""
         cfg = self.config
         if cfg.B != 1:
             raise ValueError(f'forward_trials: independent trials are B = 1 detections (config.B = {cfg.B}); '
                              'a B > 1 batch shares its scalars, its shift and its exit (use forward)')
-        if cfg.mode not in ('sparc', 'segmented'):
+        if cfg.mode not in modes:
             raise ValueError(f"forward_trials: generator_mode {cfg.mode!r} has no independent-trial form "
-                             "('sparc' and 'segmented' only)")
+                             "('sparc' and 'segmented' only; 'random': BAMP(config, random_trials=True))")
         E = len(ys)
         if not (E == len(xs) == len(symbols) == len(indices)) or E < 1:
             raise ValueError('forward_trials: ys, xs, symbols and indices must hold the same number (>= 1) of trials')

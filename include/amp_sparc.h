@@ -573,16 +573,20 @@ int amp_segmented_decide_count(const amp_dims* d, const amp_constellation* c, co
  *      ibits_trunc = ceil(log2(Lin Na)), flat indices local to the trial; loss.py:67-179) by the
  *      MAP rule (loss.py:282-302) or the segmented rule (loss.py:222-250).  Launch engine, f32
  *      GEMMs, any trials >= 1; AMP_E_ARG for the shapes amp_vamp_run / amp_bamp_run /
- *      amp_scamp_run refuse, for the persistent engine and for BAMP's element-wise denoiser
- *      ('random' mode).  SCAMP decides on xmap (scamp.py:107). */
+ *      amp_scamp_run refuse and for the persistent engine.  SCAMP decides on xmap (scamp.py:107).
+ *      generator_mode 'random' (BAMP's element-wise denoiser, amp_bamp_args.denoiser == 1, and the
+ *      rule AMP_RULE_RANDOM) is batched by amp_bamp_random_trials_run alone: amp_vamp_trials_run /
+ *      _ch_run, amp_bamp_trials_run / _ch_run and amp_scamp_trials_run / _ch_run still answer
+ *      AMP_E_ARG for that denoiser and for that rule. */
 #define AMP_RULE_SPARC 0
 #define AMP_RULE_SEGMENTED 1
+#define AMP_RULE_RANDOM 2     /* Loss.random_decision (loss.py:252-280): amp_bamp_random_trials_run only */
 typedef struct amp_trials_decide_args {
     const void* x;        /* c64 [trials][N] transmitted vectors */
     const void* sym;      /* int64 [trials][L] true gray labels (data.py:89) */
     const void* idx;      /* int64 [trials][L] true flat nonzero indices, local to the trial (data.py:90) */
     int32_t ibits_trunc;  /* ceil(log2(Lin*Na)) (loss.py:20 at B = 1) */
-    int32_t rule;         /* AMP_RULE_SPARC / AMP_RULE_SEGMENTED */
+    int32_t rule;         /* AMP_RULE_SPARC / AMP_RULE_SEGMENTED (AMP_RULE_RANDOM: amp_bamp_random_trials_run) */
     void* counts;         /* out amp_counts[trials] (device) */
 } amp_trials_decide_args;
 /* replaces `trials` calls of VAMP.forward at B = 1 (vamp.py:159-187) + Loss.error_rate.  Shapes: as
@@ -619,6 +623,27 @@ int amp_bamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const 
 size_t amp_scamp_trials_ch_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel);
 int amp_scamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const amp_scamp_args* a,
                             const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream);
+/* generator_mode 'random' (data.py:55-72: any Na of the Nt antennas per channel use, one symbol for
+ * all of them; the reference runs it at batch = 1 only, loss.py:262): `trials` calls of BAMP.forward
+ * at B = 1 with the element-wise denoiser (bamp.py:79-88, a->denoiser == 1, a->P0 / a->Ps) +
+ * Loss.error_rate by random_decision (loss.py:252-280), on one channel (per_channel >= trials) or
+ * on G = ceil(trials / per_channel) channels (a->H c64 [G][n][N]), trial e on channel
+ * e / per_channel.  It is amp_bamp_trials_ch_run's run (the same packed operators, GEMM kernels and
+ * shapes: any n, N % 4 == 2, a partial last column tile, f32 tiles) with the denoiser applied
+ * element-wise row by row: every trial is bit for bit its own amp_bamp_run at B = 1 with
+ * denoiser = 1 followed by amp_random_decide_count, with its own T_e; there is no max|xi| shift, so
+ * no float64 fix-up exists in this mode.  dec (may be NULL): rule AMP_RULE_RANDOM; per trial and
+ * channel use the Na largest |x_m| (NaN largest, exact ties by the larger index), each decided to
+ * its nearest point and compared, in ascending position order, with the trial's own sorted true
+ * indices (Ns = Lin Na, flat indices local to the trial, ibits_trunc = ceil(log2(Lin Na))).
+ * AMP_E_ARG before any pointer is read: d->B != 1, trials or per_channel < 1, G > 65535, a
+ * split-precision gemm, a->denoiser != 1, null pointers, a short workspace, with dec: a rule other
+ * than AMP_RULE_RANDOM or Na > 64, and every shape amp_bamp_run refuses.  The workspace is
+ * amp_bamp_trials_ch_run's: the query equals amp_bamp_trials_ch_workspace_bytes at the same
+ * arguments (0 where the run would refuse). */
+size_t amp_bamp_random_trials_workspace_bytes(const amp_dims* d, int32_t max_iter, int32_t trials, int32_t per_channel);
+int amp_bamp_random_trials_run(const amp_dims* d, const amp_constellation* c, const amp_bamp_args* a,
+                               const amp_trials_decide_args* dec, int32_t trials, int32_t per_channel, void* stream);
 /* The same for VAMP (vamp_model.py:45-61: the channel and its SVD are redrawn every `res` epochs).
  * The factors of the G channels lie back to back: a->U c64 [G][n][k], a->s f32 [G][k], a->Vh c64
  * [G][k][N].  Each channel's own singular values scale its packed s U^H (y~, vamp.py:22), enter its
@@ -650,7 +675,8 @@ int amp_vamp_trials_ch_run(const amp_dims* d, const amp_constellation* c, const 
  *      workspace.  AMP_E_ARG, before anything is launched: non-positive or inconsistent dims, M no
  *      power of two, N odd, d->B != 1, K not in {1, 2, 4, 8, 16, 64}, null pointers, channels /
  *      trials / per_channel < 1, more than 65535 channels, Lh outside [1, Lout], band_blocks
- *      outside [0, Lout], Nr Nt Lh beyond 32 bits, L > 4096 (the trial's section list lives in LDS). */
+ *      outside [0, Lout], Nr Nt Lh beyond 32 bits, L > 4096 (the trial's section list lives in LDS), message
+ *      outside {0, 1}. */
 typedef struct amp_synth_args {
     uint64_t seed;
     uint64_t channel0;    /* amp_synth_channels: id of channel g is channel0 + g */
@@ -664,7 +690,9 @@ typedef struct amp_synth_args {
                            * column blocks (o - Lh, o] (channels of amp_synth_channels /
                            * generate_as_sparc); 0: every section (any A) */
     float noise_std;      /* amp_synth_trials: sqrt(Na/Nr/SNR/2) (channel.py:153) */
-    int32_t pad;
+    int32_t message;      /* amp_synth_trials: 0 one point per section (Data.segmented, data.py:74-91),
+                           * 1 Na of the Nt antennas per channel use with one symbol (Data.random,
+                           * data.py:55-72) */
     void* x;              /* amp_synth_trials out: c64 [E][N] */
     void* sym;            /* out int64 [E][L] gray labels (data.py:89) */
     void* idx;            /* out int64 [E][L] flat nonzero indices, local to the trial (data.py:90) */
@@ -678,7 +706,13 @@ int amp_synth_channels(const amp_dims* d, const amp_synth_args* a, int32_t chann
 /* Trial e (id trial0 + e) on channel e / per_channel, as amp_*_trials_ch_run.  Section s takes
  * the block at index s: pos = mulhi32(w0, M), k = mulhi32(w1, K); x[s M + pos] = symbol k.  Row j
  * takes the block at index j for its noise.  y[e][j] = sum over the active columns, in ascending
- * section order, of At[g][col][j] symbol (float32, no contraction), plus the noise. */
+ * position order, of At[g][col][j] symbol (float32, no contraction), plus the noise.
+ * message = 1 (generator_mode 'random'): channel use u < Lin draws a uniformly random Na-subset of
+ * its Nt antennas by Floyd's sampling on stream 1: for j = 0 .. Na - 1, with J = Nt - Na + j,
+ * t = mulhi32(w0 of the block at index u Na + j, J + 1); antenna t is taken unless already chosen,
+ * else antenna J.  One symbol for the channel use: k = mulhi32(w1 of the block at index u Na, K).
+ * idx: the L = Na Lin flat positions u Nt + antenna in ascending order; sym: gray[k] at each of
+ * them; x, noise and y as above.  Every existing caller passes message = 0 and gets the same bits. */
 int amp_synth_trials(const amp_dims* d, const amp_constellation* c, const amp_synth_args* a, int32_t trials,
                      int32_t per_channel, void* stream);
 
