@@ -641,9 +641,14 @@ __device__ __forceinline__ void denoise_step_grid2(const P& pol, int base, int n
 // full-round step below: the posterior mean (xr, xi), the variance and the sections' max logit /
 // max |logit|.  A restatement, operation for operation, and not a function both steps share: the
 // engines that keep denoise_step_grid2 must keep their code objects unchanged.
-template <bool kVar, int R, int PAT, int G>
+// mid(er, ei): called between the exponentials and the section sums (DenPrio below; the default: no code).
+struct DenNoMid {
+    template <class T>
+    __device__ __forceinline__ void operator()(T&, T&) const {}
+};
+template <bool kVar, int R, int PAT, int G, class Mid = DenNoMid>
 __device__ __forceinline__ void grid2_core(const f2v ur, const f2v ui, const GridRegs<R>& Q, f2v& xr_out, f2v& xi_out,
-                                           f2v& var_out, f2v& smax_out, f2v& sabs_out) {
+                                           f2v& var_out, f2v& smax_out, f2v& sabs_out, Mid&& mid = Mid()) {
     constexpr bool FULLG = PAT == GRID_FULL;
     f2v X[R], Y[R];
 #pragma unroll
@@ -684,6 +689,7 @@ __device__ __forceinline__ void grid2_core(const f2v ur, const f2v ui, const Gri
         ei[i] = f2v{__builtin_amdgcn_exp2f(ya.x), __builtin_amdgcn_exp2f(ya.y)};
 #endif
     }
+    mid(er, ei);
     f2v zt, ar, ai, SI = f2splat(0.f);
     f2v Sr[FULLG ? 1 : R];
     if constexpr (FULLG) {
@@ -791,9 +797,9 @@ __device__ __forceinline__ Grid2In grid2_load(const P& pol, int base) {
     for (int u = 0; u < 2; ++u) in.vp[u] = pol.load_prev(base + u * gpw + gid, g);
     return in;
 }
-template <bool kVar, int R, int PAT, int G, class P>
+template <bool kVar, int R, int PAT, int G, class Mid = DenNoMid, class P>
 __device__ __forceinline__ void denoise_step_grid2_full(const P& pol, int base, const Grid2In& in, const GridRegs<R>& Q,
-                                                        PartAcc& pa, DenStat& S) {
+                                                        PartAcc& pa, DenStat& S, Mid&& mid = Mid()) {
     const int lane = threadIdx.x & 63;
     constexpr int gpw = 64 / G;
     const int gid = lane / G, g = lane % G;
@@ -803,7 +809,7 @@ __device__ __forceinline__ void denoise_step_grid2_full(const P& pol, int base, 
                     (int)!(fabsf(ui.y) <= FLT_MAX);
     S.st_bad |= bad != 0;
     f2v xr, xi, var, smax, sabs;
-    grid2_core<kVar, R, PAT, G>(ur, ui, Q, xr, xi, var, smax, sabs);
+    grid2_core<kVar, R, PAT, G>(ur, ui, Q, xr, xi, var, smax, sabs, mid);
     pol.store_xv(base + gid, g, xr.x, xi.x, var.x);
     pol.store_xv(base + gpw + gid, g, xr.y, xi.y, var.y);
 #pragma unroll
@@ -832,9 +838,9 @@ __device__ __forceinline__ void denoise_step_grid2_full(const P& pol, int base, 
 //         exactly positions 2j and 2j + 1: with a, b the lane's two values, excl_a = 0 + b,
 //         excl_b = 0 + a, tot = a + b, then the DPP distances 1, 2, 4, 8 over j are the old
 //         2, 4, 8, 16 (float addition is commutative: the same tree term for term).
-template <bool kVar, int R, int PAT>
+template <bool kVar, int R, int PAT, class Mid = DenNoMid>
 __device__ __forceinline__ void grid2_pair_core(const f2v ur, const f2v ui, const GridRegs<R>& Q, f2v& xr_out, f2v& xi_out,
-                                                f2v& var_out, float& smax_out, float& sabs_out) {
+                                                f2v& var_out, float& smax_out, float& sabs_out, Mid&& mid = Mid()) {
     constexpr bool FULLG = PAT == GRID_FULL;
     f2v X[R], Y[R];
 #pragma unroll
@@ -881,6 +887,7 @@ __device__ __forceinline__ void grid2_pair_core(const f2v ur, const f2v ui, cons
         ei[i] = f2v{__builtin_amdgcn_exp2f(ya.x), __builtin_amdgcn_exp2f(ya.y)};
 #endif
     }
+    mid(er, ei);
     f2v zt, ar, ai, SI = f2splat(0.f);
     f2v Sr[FULLG ? 1 : R];
     if constexpr (FULLG) {
@@ -1021,9 +1028,10 @@ __device__ __forceinline__ GridPairIn grid2_pair_load(const P& pol, int base, in
     asm volatile("" : "+v"(in.vp));
     return in;
 }
-template <bool kVar, int R, int PAT, class P>
+template <bool kVar, int R, int PAT, class Mid = DenNoMid, class P>
 __device__ __forceinline__ void denoise_step_grid2_pair(const P& pol, int base, int lane, const GridPairIn& in,
-                                                        const GridRegs<R>& Q, PartAcc& pa, double& acc, DenStat& S) {
+                                                        const GridRegs<R>& Q, PartAcc& pa, double& acc, DenStat& S,
+                                                        Mid&& mid = Mid()) {
     const int sec = base + (lane >> 4), m = 2 * (lane & 15);
     const f2v it = f2splat(pol.inv);
     const f2v ur = in.rr * it, ui = in.ri * it;   // c64 / f32 == multiply by the reciprocal
@@ -1032,7 +1040,7 @@ __device__ __forceinline__ void denoise_step_grid2_pair(const P& pol, int base, 
     S.st_bad |= bad != 0;
     f2v xr, xi, var;
     float smax, sabs;
-    grid2_pair_core<kVar, R, PAT>(ur, ui, Q, xr, xi, var, smax, sabs);
+    grid2_pair_core<kVar, R, PAT>(ur, ui, Q, xr, xi, var, smax, sabs, mid);
     pol.store_xv2(sec, m, make_float4(xr.x, xi.x, xr.y, xi.y), make_float2(var.x, var.y));
     // lanes < 32: var.x of sections base + gid, base + 2 + gid; lanes >= 32: var.y of the same two
     const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(var.x), __float_as_uint(var.y), false, false);
@@ -1066,8 +1074,82 @@ constexpr int grid_r() { return KK == 4 ? 2 : KK == 16 ? 4 : KK == 64 ? 8 : 0; }
 // supplies load_r2 / load_prev2 / store_xv2 / account_close); the same bits again.
 // (Requesting the next round's inputs before the current round's arithmetic was measured slower:
 // the six values held across the step spilled)
-template <bool kVar, int KK, int U, int G, bool PKG = true, int FAST = DEN_FAST_NONE, class P>
-__device__ __forceinline__ bool denoise_sections_grid(const P& pol, int nsec, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block()) {
+//
+// PRIO (vamp_persist's eight-wave bf16x3 kernels, two waves per SIMD: AMP_X3_DEN_PRIO): the issue priority of
+// this wave through its full rounds (DEN_FAST_PAIR / DEN_FAST_FULL; the masked remainder and every other
+// form run at priority 0), by the half it belongs to (half: wave-uniform, in an SGPR, as x3_gemm_prio takes
+// it; 0 the SIMD's older wave, 1 the younger).  0: none, no code.  1: the younger half at priority 1
+// throughout.  2: priority 1 in alternate rounds, the younger half in even rounds and the older in odd ones,
+// set at the top of a round.  3: as 2, and flipped once more inside the step, between the exponentials and
+// the section sums: the two waves stand half a step apart (the top of a round then changes nothing but in
+// round 0).  4: the younger half at priority 1 from the top of every round to that point, the older half
+// from there to the round's end.  5, 6: the younger half at priority 1 through its first two / three rounds
+// and at 0 from then on (age decides again: the older half runs ahead for the rest), so that the halves end
+// together instead of one running half its rounds alone (6 is vamp_persist's default: DESIGN.md §3.3).
+// s_setprio takes an immediate, so each one stands behind a scalar branch; every form leaves the loop at
+// priority 0, also a wave without a full round (it never raised it).  Only the time at which instructions
+// issue differs.
+template <int PRIO>
+struct DenPrio {
+    int half, p, rd;   // p: this wave's priority from the next top() on (forms 2, 3); rd: its round (forms 5, 6)
+    __device__ __forceinline__ explicit DenPrio(int h) : half(h), p(h), rd(0) {}
+    __device__ __forceinline__ static void set(int one) {
+        if (one) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+    }
+    __device__ __forceinline__ void top() {
+        if constexpr (PRIO == 1) {
+            if (half) __builtin_amdgcn_s_setprio(1);
+        } else if constexpr (PRIO == 2) {
+            set(p);
+            p ^= 1;
+        } else if constexpr (PRIO == 3) {
+            set(p);
+        } else if constexpr (PRIO == 4) {
+            set(half);
+        } else if constexpr (PRIO == 5 || PRIO == 6) {
+            if (half) {
+                if (rd == 0) __builtin_amdgcn_s_setprio(1);
+                else if (rd == PRIO - 3) __builtin_amdgcn_s_setprio(0);
+            }
+            ++rd;
+        }
+    }
+    // (the compiler is free to move s_setprio over plain arithmetic, and put it ahead of the exponentials: the
+    // exponentials' results go through an empty asm on either side of it, which holds them behind it and the
+    // sums ahead of it.  The pins change the operand order of the sums behind them: finite results keep their
+    // bits, a NaN row's NaNs come out with another payload, so forms 3 and 4 are for timing A/B runs only)
+    __device__ __forceinline__ static void pin(f2v (&er)[4], f2v (&ei)[4]) {
+        asm volatile("" : "+v"(er[0]), "+v"(er[1]), "+v"(er[2]), "+v"(er[3]), "+v"(ei[0]), "+v"(ei[1]), "+v"(ei[2]), "+v"(ei[3]));
+    }
+    __device__ __forceinline__ void operator()(f2v (&er)[4], f2v (&ei)[4]) {   // grid2_core's / grid2_pair_core's mid()
+        if constexpr (PRIO == 3 || PRIO == 4) {
+            pin(er, ei);
+            if constexpr (PRIO == 3) {
+                p ^= 1;
+                set(p);
+            } else {
+                set(half ^ 1);
+            }
+            pin(er, ei);
+        }
+    }
+    __device__ __forceinline__ void leave() const {
+        if constexpr (PRIO == 1 || PRIO == 5 || PRIO == 6) {
+            if (half) __builtin_amdgcn_s_setprio(0);
+        } else if constexpr (PRIO != 0) {
+            if (half) __builtin_amdgcn_s_setprio(0);
+            else __builtin_amdgcn_s_setprio(0);
+        }
+    }
+};
+// hook(rd): called behind full round rd of this wave (the trace builds' per-round stamps; the default: no code)
+struct DenNoHook {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+template <bool kVar, int KK, int U, int G, bool PKG = true, int FAST = DEN_FAST_NONE, int PRIO = 0, class Hook = DenNoHook, class P>
+__device__ __forceinline__ bool denoise_sections_grid(const P& pol, int nsec, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block(),
+                                                      int half = 0, Hook&& hook = Hook()) {
     constexpr int R = grid_r<KK>();
     if constexpr (R == 0) {
         return false;
@@ -1091,20 +1173,29 @@ __device__ __forceinline__ bool denoise_sections_grid(const P& pol, int nsec, co
             int base = wave * gpw * U;
             if constexpr (FAST && PKG && U == 2 && AMP_DEN_PACKED_GRID) {
                 const int step = nw * gpw * 2;
+                DenPrio<PRIO> pr(half);
+                int rd = 0;   // (the hook's round index: dead without one)
                 if constexpr (FAST == DEN_FAST_PAIR && G == 32) {
                     // (a wave without a full round moves its sums there and back: no branch around the loop;
                     // the wave-uniform base as a scalar: the loop branches on SCC, not on an exec mask)
                     base = __builtin_amdgcn_readfirstlane(base);
                     double acc = pair_acc_in(pa.sumvar);
                     for (; base + 2 * gpw <= nsec; base += step) {
+                        pr.top();
                         const int lane = pair_lane();   // the step's addresses formed in the step
                         denoise_step_grid2_pair<kVar, R, GRID_REF16>(pol, base, lane, grid2_pair_load(pol, base, lane), Q, pa,
-                                                                     acc, S);
+                                                                     acc, S, pr);
+                        hook(rd++);
                     }
+                    pr.leave();
                     pa.sumvar = pair_acc_out(acc);
                 } else {
-                    for (; base + 2 * gpw <= nsec; base += step)
-                        denoise_step_grid2_full<kVar, R, GRID_REF16, G>(pol, base, grid2_load<G>(pol, base), Q, pa, S);
+                    for (; base + 2 * gpw <= nsec; base += step) {
+                        pr.top();
+                        denoise_step_grid2_full<kVar, R, GRID_REF16, G>(pol, base, grid2_load<G>(pol, base), Q, pa, S, pr);
+                        hook(rd++);
+                    }
+                    pr.leave();
                 }
             }
             for (; base < nsec; base += nw * gpw * U) {
@@ -1145,25 +1236,28 @@ __device__ __forceinline__ void denoise_sections_gp(const P& pol, int nsec, cons
 enum { PK_NONE = 0, PK_ALL = 1, PK_GRID = 2 };
 
 // Runtime M (a power of two <= 64) -> the compile-time group size.
-template <bool kVar, int KK, int U, int G, int PK, int FAST = DEN_FAST_NONE, class P>
-__device__ __forceinline__ void denoise_sections_sel(const P& pol, int nsec, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block()) {
+// (PRIO, half, hook: denoise_sections_grid's, for its full rounds alone)
+template <bool kVar, int KK, int U, int G, int PK, int FAST = DEN_FAST_NONE, int PRIO = 0, class Hook = DenNoHook, class P>
+__device__ __forceinline__ void denoise_sections_sel(const P& pol, int nsec, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block(),
+                                                     int half = 0, Hook&& hook = Hook()) {
     if constexpr (PK == PK_ALL && KK % 2 == 0) {
         denoise_sections_gp<kVar, KK, U, G>(pol, nsec, c, pa, dw);
     } else {
-        if (denoise_sections_grid<kVar, KK, U, G, PK == PK_GRID, FAST>(pol, nsec, c, pa, dw)) return;
+        if (denoise_sections_grid<kVar, KK, U, G, PK == PK_GRID, FAST, PRIO>(pol, nsec, c, pa, dw, half, hook)) return;
         denoise_sections_g<kVar, KK, U, G>(pol, nsec, c, pa, dw);
     }
 }
-template <bool kVar, int KK, int U, int PK = PK_ALL, int FAST = DEN_FAST_NONE, class P>
-__device__ __forceinline__ void denoise_sections_u(const P& pol, int nsec, int M, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block()) {
+template <bool kVar, int KK, int U, int PK = PK_ALL, int FAST = DEN_FAST_NONE, int PRIO = 0, class Hook = DenNoHook, class P>
+__device__ __forceinline__ void denoise_sections_u(const P& pol, int nsec, int M, const Const& c, PartAcc& pa, DenWaves dw = DenWaves::block(),
+                                                   int half = 0, Hook&& hook = Hook()) {
     switch (M) {
-    case 64: denoise_sections_sel<kVar, KK, U, 64, PK, FAST>(pol, nsec, c, pa, dw); break;
-    case 32: denoise_sections_sel<kVar, KK, U, 32, PK, FAST>(pol, nsec, c, pa, dw); break;
-    case 16: denoise_sections_sel<kVar, KK, U, 16, PK, FAST>(pol, nsec, c, pa, dw); break;
-    case 8: denoise_sections_sel<kVar, KK, U, 8, PK, FAST>(pol, nsec, c, pa, dw); break;
-    case 4: denoise_sections_sel<kVar, KK, U, 4, PK, FAST>(pol, nsec, c, pa, dw); break;
-    case 2: denoise_sections_sel<kVar, KK, U, 2, PK, FAST>(pol, nsec, c, pa, dw); break;
-    default: denoise_sections_sel<kVar, KK, U, 1, PK, FAST>(pol, nsec, c, pa, dw); break;
+    case 64: denoise_sections_sel<kVar, KK, U, 64, PK, FAST, PRIO>(pol, nsec, c, pa, dw, half, hook); break;
+    case 32: denoise_sections_sel<kVar, KK, U, 32, PK, FAST, PRIO>(pol, nsec, c, pa, dw, half, hook); break;
+    case 16: denoise_sections_sel<kVar, KK, U, 16, PK, FAST, PRIO>(pol, nsec, c, pa, dw, half, hook); break;
+    case 8: denoise_sections_sel<kVar, KK, U, 8, PK, FAST, PRIO>(pol, nsec, c, pa, dw, half, hook); break;
+    case 4: denoise_sections_sel<kVar, KK, U, 4, PK, FAST, PRIO>(pol, nsec, c, pa, dw, half, hook); break;
+    case 2: denoise_sections_sel<kVar, KK, U, 2, PK, FAST, PRIO>(pol, nsec, c, pa, dw, half, hook); break;
+    default: denoise_sections_sel<kVar, KK, U, 1, PK, FAST, PRIO>(pol, nsec, c, pa, dw, half, hook); break;
     }
 }
 

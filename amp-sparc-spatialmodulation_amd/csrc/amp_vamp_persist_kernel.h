@@ -16,6 +16,7 @@ namespace amp {
 
 constexpr int AMP_TRACE_STRIDE = 10;   // diagnostic stamps per (workgroup, iteration)
 constexpr int AMP_TRACE_SEAM = 24;     // AMP_WAVE_TAIL_ARRIVAL = 9: per wave, two arrivals and a fallback word
+constexpr int AMP_TRACE_DEN = 16;      // AMP_DEN_TRACE = 1: eight ends of the denoiser, four round ends of wave 0, four of wave 4
 #ifndef AMP_OCC2_PK
 #define AMP_OCC2_PK 0                   // 1: the packed denoiser also at two waves per SIMD (diagnostic builds)
 #endif
@@ -79,6 +80,14 @@ constexpr int AMP_TRACE_SEAM = 24;     // AMP_WAVE_TAIL_ARRIVAL = 9: per wave, t
 #ifndef AMP_X3_GEMM2_PRIO
 #define AMP_X3_GEMM2_PRIO AMP_X3_GEMM_PRIO   // ... and through GEMM2
 #endif
+#ifndef AMP_X3_DEN_PRIO
+#define AMP_X3_DEN_PRIO 6               // the same kernels: wave priority through the denoiser's full rounds (amp_denoise.h
+#endif                                  // DenPrio: 6, the younger half at priority 1 through its first three rounds, so that
+                                        // the SIMD's two waves end together; A/B builds: 0 ... 5)
+#ifndef AMP_DEN_TRACE
+#define AMP_DEN_TRACE 0                 // trace builds only: 1 stamps every wave where it leaves the denoiser, and waves 0 and
+#endif                                  // 4 behind each of their first four full rounds, in the words behind the seam words
+                                        // (AMP_TRACE_DEN per (workgroup, iteration): tools/trace_persist.py sizes the buffer)
 
 // LDS carve (floats).  Row strides 2N+4 / max(2N,2k)+4 keep the f32 engine's 16-row ds_read_b128
 // and accumulator stores conflict-free (row r and r+4 land 16 banks apart); the split-precision
@@ -190,6 +199,10 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
     // (at M = 32 its position-pair form, denoise_step_grid2_pair)
     constexpr int DENFAST = !(NWV == 8 && OCC == 1 && PKDEN == PK_GRID && AMP_X3_W8_DENFAST) ? DEN_FAST_NONE
                             : AMP_X3_W8_DENPAIR ? DEN_FAST_PAIR : DEN_FAST_FULL;
+    // the bf16x3 ones of those kernels (the int8x4 eight-wave form keeps its code): the waves' issue priority
+    // through those full rounds (amp_denoise.h DenPrio), and the trace builds' per-wave stamps of the denoiser
+    constexpr int DENPRIO = (DENFAST != DEN_FAST_NONE && X3 && !H2 && !I8) ? AMP_X3_DEN_PRIO : 0;
+    constexpr bool DENTR = DENFAST != DEN_FAST_NONE && X3 && !H2 && !I8 && AMP_DEN_TRACE != 0;
     constexpr int PWG = 64 * NWV;
     constexpr int NC = X3 ? NT / 2 : 1;        // complex column tiles per wave (X3)
     constexpr int G3 = NT * NWV / 4;           // 32-wide complex reduction groups: N / 32
@@ -1085,6 +1098,21 @@ __global__ __launch_bounds__(64 * NWV, OCC * NWV / 4) void vamp_persist(VampK P_
         stamp(t, 4);
         if constexpr (KK > 16)
             denoise_sections_wide_m<true, KK>(pol, nrows * spr, M, P.c, pa);
+        else if constexpr (DENTR) {   // trace builds: every wave's end of the denoiser, waves 0 and 4 behind each full round
+            const int wvd = __builtin_amdgcn_readfirstlane(wave);
+            unsigned long long* const dtw =
+                (trc && t < P.max_iter) ? trc + (size_t)nwg * P.max_iter * (AMP_TRACE_STRIDE + 1 + AMP_TRACE_SEAM) + 4 * nwg +
+                                              ((size_t)wg * P.max_iter + t) * AMP_TRACE_DEN
+                                        : nullptr;
+            auto round_stamp = [&](int rd) __attribute__((always_inline)) {
+                if (dtw && lane == 0 && (wvd & 3) == 0 && rd < 4) dtw[8 + wvd + rd] = __builtin_amdgcn_s_memtime();
+            };
+            denoise_sections_u<true, KK, DU, PKDEN, DENFAST, DENPRIO>(pol, nrows * spr, M, P.c, pa, DenWaves::block(), wvd >> 2,
+                                                                      round_stamp);
+            if (dtw && lane == 0) dtw[wvd] = __builtin_amdgcn_s_memtime();
+        } else if constexpr (DENPRIO != 0)   // waves 4-7 are the SIMDs' second, younger set
+            denoise_sections_u<true, KK, DU, PKDEN, DENFAST, DENPRIO>(pol, nrows * spr, M, P.c, pa, DenWaves::block(),
+                                                                      __builtin_amdgcn_readfirstlane(wave) >> 2);
         else
             denoise_sections_u<true, KK, DU, PKDEN, DENFAST>(pol, nrows * spr, M, P.c, pa);   // two waves per SIMD: scalar f32 (amp_denoise.h)
         stamp(t, 8);

@@ -23,6 +23,8 @@ PHASES = ['r~ build', 'GEMM1', 'w store', 'GEMM2 + r', 'denoiser', 'partial publ
 STRIDE = 10   # stamps per (workgroup, iteration): amp_vamp_persist.hip AMP_TRACE_STRIDE
 SEAM = 24     # AMP_TRACE_SEAM: per (workgroup, iteration) eight arrivals at GEMM1's closing barrier, eight at
               # GEMM2's, eight pack-ahead fallback words (libraries built with AMP_WAVE_TAIL_ARRIVAL=9 only)
+DEN = 16      # AMP_TRACE_DEN: behind them, per (workgroup, iteration), every wave's end of the denoiser and the ends of
+              # the first four full rounds of waves 0 and 4 (libraries built with AMP_DEN_TRACE=1 only)
 # stamp slots in time order.  The exchange's three phases: slot 8 (this wave's denoiser done) -> 5 is the
 # partial publish (wave tree, both barriers, thread 0's fold and granule stores: it waits for the SIMD's
 # partner wave), 5 -> 6 the gather (sweep, lane fold, tree, LDS broadcast), 6 -> 7 the scalars (the all-NaN
@@ -105,8 +107,8 @@ def main():
     T = det.detect(inp['U'], inp['s'], inp['Vh'], inp['y'], inp['SNR'])
     nwg = (B + 15) // 16
     # ten stamps per (workgroup, iteration), 4 nwg start / end clock words, then the gathers' sweep counts
-    # (and the seam words of an AMP_WAVE_TAIL_ARRIVAL=9 library)
-    tr = torch.zeros(nwg * iters * STRIDE + 4 * nwg + nwg * iters + nwg * iters * SEAM, dtype=torch.int64, device=dev)
+    # (and the seam words of an AMP_WAVE_TAIL_ARRIVAL=9 library, the denoiser words of an AMP_DEN_TRACE=1 one)
+    tr = torch.zeros(nwg * iters * STRIDE + 4 * nwg + nwg * iters + nwg * iters * (SEAM + DEN), dtype=torch.int64, device=dev)
     s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s0.record()
     b0 = nat.prepare_counts()
@@ -144,6 +146,7 @@ def main():
               f'vamp_advance median {np.median(raw[:, :, 7] - raw[:, :, 9]):.0f} cycles')
     sweep_counts(a, nwg, iters, Tn)
     seam_arrivals(a, nwg, iters, Tn)
+    denoiser_ends(a, nwg, iters, Tn)
     arrival_spread(a, st, nwg, iters, Tn)
 
 
@@ -165,6 +168,35 @@ def seam_arrivals(a, nwg, iters, Tn):
     fb = a[base:base + nwg * iters * SEAM].reshape(nwg, iters, SEAM)[:, :Tn, 16:24]
     print(f'  pack-ahead fallbacks: {int(fb.sum())} of {fb.size} (wave, workgroup, iteration); iteration 0: {int(fb[:, 0].sum())}; '
           f'per wave: {[int(v) for v in fb.sum(axis=(0, 1))]}')
+
+
+def denoiser_ends(a, nwg, iters, Tn):
+    """Each wave's end of the denoiser (cycles behind stamp 4), the round times of waves 0 and 4 (the SIMD 0
+    pair: the older and the younger wave) and the publish chain alone, from the last wave's end to stamp 5.
+    Written by an AMP_DEN_TRACE=1 library only (the kernels with the full-round denoiser step)."""
+    base = nwg * iters * STRIDE + 4 * nwg + nwg * iters + nwg * iters * SEAM
+    dn = a[base:base + nwg * iters * DEN].reshape(nwg, iters, DEN).astype(np.int64)[:, 1:Tn]
+    raw = a[:nwg * iters * STRIDE].reshape(nwg, iters, STRIDE).astype(np.int64)[:, 1:Tn]
+    if dn.size == 0 or not np.all(dn[:, :, :8] > 0):
+        print('  denoiser ends: not recorded by this library')
+        return
+    ends = dn[:, :, :8] - raw[:, :, 4, None]
+    med = np.median(ends, axis=(0, 1))
+    print('  end of the denoiser (median cycles behind stamp 4, waves 0-7): ' + ' '.join(f'{v:.0f}' for v in med)
+          + f'  halves: {np.median(ends[:, :, :4]):.0f} | {np.median(ends[:, :, 4:]):.0f}'
+          + f'  younger - older per SIMD: {np.median(ends[:, :, 4:] - ends[:, :, :4]):.0f}')
+    for w, lo in ((0, 8), (4, 12)):
+        full = np.all(dn[:, :, lo:lo + 4] > 0, axis=2)   # workgroups with four full rounds in this wave
+        if not full.any():
+            continue
+        st = np.concatenate([raw[:, :, 4, None], dn[:, :, lo:lo + 4]], axis=2)[full]
+        print(f'  wave {w}: rounds (median cycles each) ' + ' '.join(f'{v:.0f}' for v in np.median(np.diff(st, axis=1), axis=0))
+              + f'  last round\'s end {np.median(st[:, 4] - st[:, 0]):.0f}')
+    last = dn[:, :, :8].max(axis=2)
+    print(f'  publish chain alone (last wave\'s end -> stamp 5): median {np.median(raw[:, :, 5] - last):.0f}  '
+          f'p10 {np.percentile(raw[:, :, 5] - last, 10):.0f}  p90 {np.percentile(raw[:, :, 5] - last, 90):.0f};  '
+          f'last end: median {np.median(last - raw[:, :, 4]):.0f};  denoiser + publish (4 -> 5): median '
+          f'{np.median(raw[:, :, 5] - raw[:, :, 4]):.0f}')
 
 
 def sweep_counts(a, nwg, iters, Tn):

@@ -13,7 +13,9 @@
 
 using namespace amp;
 
-template <int KK, int U, int NWV, int PK, int FAST = 0>
+// PRIO: the waves' issue priority through the full rounds (amp_denoise.h DenPrio; waves NWV / 2 ... are the
+// SIMDs' second, younger set)
+template <int KK, int U, int NWV, int PK, int FAST = 0, int PRIO = 0>
 __global__ __launch_bounds__(64 * NWV, 1) void ub(const float* rin, Const c, int N, int M, float inv, int reps,
                                                 unsigned long long* out, double* sink) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -34,6 +36,10 @@ __global__ __launch_bounds__(64 * NWV, 1) void ub(const float* rin, Const c, int
     unsigned long long t0 = __builtin_amdgcn_s_memtime();
     for (int r = 0; r < reps; ++r) {
         PDenoisePolicy pol{sR, sX, (r & 1) ? v1 : v0, (r & 1) ? v0 : v1, sm, sa, ldr, M, 31 - __builtin_clz(spr), N, inv};
+        if constexpr (PRIO != 0)
+            denoise_sections_u<true, KK, U, PK, FAST, PRIO>(pol, 16 * spr, M, c, pa, DenWaves::block(),
+                                                            __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) / (NWV / 2));
+        else
         denoise_sections_u<true, KK, U, PK, FAST>(pol, 16 * spr, M, c, pa);
         __syncthreads();
     }
@@ -43,17 +49,17 @@ __global__ __launch_bounds__(64 * NWV, 1) void ub(const float* rin, Const c, int
     if ((threadIdx.x & 63) == 0) sink[blockIdx.x * NWV + (threadIdx.x >> 6)] = pa.sumvar + pa.notclose;
 }
 
-template <int KK, int U, int NWV, int PK, int FAST = 0>
+template <int KK, int U, int NWV, int PK, int FAST = 0, int PRIO = 0>
 static void run(const char* tag, const float* dr, const Const& c, int N, int M, float inv, unsigned long long* dout,
                 double* dsink) {
     const int nwg = 256, reps = 20;
     const size_t lds = (size_t)(2 * 16 * (2 * N + 4) + 2 * 16 * N + 2 * 16 * (N / M)) * 4;
-    hipFuncSetAttribute((const void*)ub<KK, U, NWV, PK, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    for (int w = 0; w < 2; ++w) hipLaunchKernelGGL((ub<KK, U, NWV, PK, FAST>), dim3(nwg), dim3(64 * NWV), lds, 0, dr, c, N, M, inv, reps, dout, dsink);
+    hipFuncSetAttribute((const void*)ub<KK, U, NWV, PK, FAST, PRIO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    for (int w = 0; w < 2; ++w) hipLaunchKernelGGL((ub<KK, U, NWV, PK, FAST, PRIO>), dim3(nwg), dim3(64 * NWV), lds, 0, dr, c, N, M, inv, reps, dout, dsink);
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0);
-    hipLaunchKernelGGL((ub<KK, U, NWV, PK, FAST>), dim3(nwg), dim3(64 * NWV), lds, 0, dr, c, N, M, inv, reps, dout, dsink);
+    hipLaunchKernelGGL((ub<KK, U, NWV, PK, FAST, PRIO>), dim3(nwg), dim3(64 * NWV), lds, 0, dr, c, N, M, inv, reps, dout, dsink);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms;
@@ -61,8 +67,8 @@ static void run(const char* tag, const float* dr, const Const& c, int N, int M, 
     std::vector<unsigned long long> h(nwg);
     hipMemcpy(h.data(), dout, nwg * 8, hipMemcpyDeviceToHost);
     std::sort(h.begin(), h.end());
-    printf("%-28s K=%2d U=%d waves=%d pk=%d fast=%d  median %7llu cyc/call  p90 %7llu  (kernel %.3f ms / %d reps)\n", tag, KK, U, NWV, (int)PK, (int)FAST,
-           h[nwg / 2], h[nwg * 9 / 10], ms, reps);
+    printf("%-28s K=%2d U=%d waves=%d pk=%d fast=%d prio=%d  median %7llu cyc/call  p90 %7llu  (kernel %.3f ms / %d reps)\n", tag, KK, U, NWV, (int)PK, (int)FAST,
+           PRIO, h[nwg / 2], h[nwg * 9 / 10], ms, reps);
 }
 
 extern "C" int ubench_main() {
@@ -109,6 +115,14 @@ extern "C" int ubench_main() {
     run<16, 2, 8, PK_GRID, false>("cfg4 16QAM packed grid", dr, c, N, M, inv, dout, dsink);
     run<16, 2, 8, PK_GRID, DEN_FAST_FULL>("cfg4 16QAM packed grid", dr, c, N, M, inv, dout, dsink);
     // and its position-pair form at M = 32 (two positions of one section per lane)
+    run<16, 2, 8, PK_GRID, DEN_FAST_PAIR>("cfg4 16QAM packed grid pair", dr, c, N, M, inv, dout, dsink);
+    // the pair form under each priority policy (AMP_X3_DEN_PRIO's forms), then the plain one once more
+    run<16, 2, 8, PK_GRID, DEN_FAST_PAIR, 1>("cfg4 16QAM packed grid pair", dr, c, N, M, inv, dout, dsink);
+    run<16, 2, 8, PK_GRID, DEN_FAST_PAIR, 2>("cfg4 16QAM packed grid pair", dr, c, N, M, inv, dout, dsink);
+    run<16, 2, 8, PK_GRID, DEN_FAST_PAIR, 3>("cfg4 16QAM packed grid pair", dr, c, N, M, inv, dout, dsink);
+    run<16, 2, 8, PK_GRID, DEN_FAST_PAIR, 4>("cfg4 16QAM packed grid pair", dr, c, N, M, inv, dout, dsink);
+    run<16, 2, 8, PK_GRID, DEN_FAST_PAIR, 5>("cfg4 16QAM packed grid pair", dr, c, N, M, inv, dout, dsink);
+    run<16, 2, 8, PK_GRID, DEN_FAST_PAIR, 6>("cfg4 16QAM packed grid pair", dr, c, N, M, inv, dout, dsink);
     run<16, 2, 8, PK_GRID, DEN_FAST_PAIR>("cfg4 16QAM packed grid pair", dr, c, N, M, inv, dout, dsink);
     fflush(stdout);
     return 0;
