@@ -81,6 +81,15 @@ class AmpSynthArgs(C.Structure):
                 ('noise', C.c_void_p)]
 
 
+EIGH_MAX_K, EIGH_MAX_SWEEPS = 640, 24   # include/amp_sparc.h AMP_EIGH_MAX_K / AMP_EIGH_MAX_SWEEPS
+
+
+class AmpEighArgs(C.Structure):
+    _fields_ = [('G', C.c_void_p), ('E', C.c_void_p), ('w', C.c_void_p), ('info', C.c_void_p),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('tol', C.c_double),
+                ('max_sweeps', C.c_int32)]
+
+
 class AmpVampShard(C.Structure):
     _fields_ = [('xbuf', C.c_void_p), ('xbuf_bytes', C.c_size_t), ('B_global', C.c_int32), ('row_offset', C.c_int32),
                 ('gen', C.c_uint32), ('pad', C.c_int32)]
@@ -174,6 +183,10 @@ SIGNATURES = {
     # the trial batches' inputs drawn on the device (synth.py)
     'amp_synth_channels': (C.c_int, [_D, C.POINTER(AmpSynthArgs), _I, _P]),
     'amp_synth_trials': (C.c_int, [_D, _K, C.POINTER(AmpSynthArgs), _I, _I, _P]),
+    # batched Jacobi eigensolver of Gram-matrix stacks (model.svd_gram method='jacobi')
+    'amp_eigh_workspace_bytes': (C.c_size_t, [_I, _I]),
+    'amp_eigh_run': (C.c_int, [C.POINTER(AmpEighArgs), _I, _I, _P]),
+    'amp_eigh_debug_readback': (C.c_int, [_I]),
     'amp_bamp_workspace_bytes': (C.c_size_t, [_D, _I]),
     'amp_bamp_run': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),
     'amp_bamp_prepare': (C.c_int, [_D, _K, C.POINTER(AmpBampArgs), _P]),

@@ -61,7 +61,79 @@ def _broadcast_seed() -> int:
     return int(base.cpu().item())
 
 
-def svd_gram(A: torch.Tensor, max_cond: float = 20.0):
+_JACOBI_CHUNK_BYTES = 1 << 30     # svd_gram(method='jacobi'): the complex128 copies of one chunk of channels
+
+
+def _jacobi_chunk(G: int, n: int, N: int) -> int:
+    """Channels per solver call: the complex128 copies of a chunk (its Gram matrices, E, the solver's
+    work matrix; one channel's A and other factor at a time) stay under 1 GiB, and the chunks of a
+    stack are of equal size, so that no call is left with a handful of channels."""
+    k = min(n, N)
+    cap = max(1, (_JACOBI_CHUNK_BYTES - 32 * n * N) // (48 * k * k))
+    return -(-G // -(-G // cap))
+
+
+def _svd_jacobi(A: torch.Tensor, max_cond: float):
+    """svd_gram(method='jacobi') on a [G, n, N] complex64 ROCm stack; None where the eigh path has
+    to take over (k above the solver's cap)."""
+    import ctypes as C
+    import warnings
+    import amp_native as nat
+    G, n, N = A.shape
+    k, tall = min(n, N), n >= N
+    if k > nat.EIGH_MAX_K:
+        return None
+    lib = nat.lib()
+    dev = A.device
+    U = torch.empty(G, n, k, dtype=torch.complex64, device=dev)
+    s = torch.empty(G, k, dtype=torch.float32, device=dev)
+    Vh = torch.empty(G, k, N, dtype=torch.complex64, device=dev)
+    info = torch.empty(G, 2, dtype=torch.int32, device=dev)
+    s64 = torch.empty(G, k, dtype=torch.float64, device=dev)
+    step = _jacobi_chunk(G, n, N)
+    for g0 in range(0, G, step):
+        g1 = min(G, g0 + step)
+        gram = torch.empty(g1 - g0, k, k, dtype=torch.complex128, device=dev)
+        # one 2-D product per channel: a channel's bits do not depend on how many share the call
+        for g in range(g1 - g0):
+            Ag = A[g0 + g].to(torch.complex128)
+            torch.mm(Ag.mH, Ag, out=gram[g]) if tall else torch.mm(Ag, Ag.mH, out=gram[g])
+        E = torch.empty_like(gram)
+        w = s64[g0:g1]
+        a = nat.AmpEighArgs()
+        a.G, a.E = nat.dptr(gram, torch.complex128, 'gram'), nat.dptr(E, torch.complex128, 'E')
+        a.w, a.info = nat.dptr(w, torch.float64, 'w'), nat.dptr(info[g0:g1], torch.int32, 'info')
+        need = lib.amp_eigh_workspace_bytes(k, g1 - g0)
+        ws = nat.WORKSPACE.get(dev, 'eigh', need)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), need
+        a.tol, a.max_sweeps = 0.0, 0
+        nat.check(lib.amp_eigh_run(C.byref(a), k, g1 - g0, nat.stream_ptr(dev)), 'amp_eigh_run')
+        sg = w.sqrt()
+        for g in range(g1 - g0):
+            Ag = A[g0 + g].to(torch.complex128)
+            if tall:                               # E = V:  U = A V / s
+                U[g0 + g] = torch.mm(Ag, E[g]) / sg[g].unsqueeze(-2)
+                Vh[g0 + g] = E[g].mH
+            else:                                  # E = U:  Vh = U^H A / s
+                U[g0 + g] = E[g]
+                Vh[g0 + g] = torch.mm(E[g].mH, Ag) / sg[g].unsqueeze(-1)
+        s[g0:g1] = sg
+    # the existing max_cond rule, on the float64 singular values
+    ok = s64[:, -1].sqrt() * max_cond > s64[:, 0].sqrt()
+    bad = (info[:, 1] == 0) & ok
+    state = torch.stack([ok.all(), bad.any()]).tolist()
+    if not state[0]:
+        return torch.linalg.svd(A, full_matrices=False)
+    if state[1]:
+        redo = torch.nonzero(bad).flatten().tolist()
+        warnings.warn(f'svd_gram(method=\'jacobi\'): {len(redo)} of {G} channels did not converge; redone by the '
+                      'eigh path', RuntimeWarning, stacklevel=3)
+        for g in redo:
+            U[g], s[g], Vh[g] = svd_gram(A[g], max_cond)
+    return U, s, Vh
+
+
+def svd_gram(A: torch.Tensor, max_cond: float = 20.0, method: str = 'eigh'):
     """Thin SVD of a full-rank matrix through the Hermitian eigendecomposition of its Gram matrix
     (the smaller of A^H A / A A^H; torch.linalg.eigh), for Model(rng='device'): on MI355X 6.8 ms
     per cfg4 channel (512 x 256 c64) against 28.9 ms for torch.linalg.svd, and closer to exact
@@ -70,7 +142,32 @@ def svd_gram(A: torch.Tensor, max_cond: float = 20.0):
     factors' orthogonality error grows as eps kappa^2: 4e-6 at kappa 6), so a channel with
     s_max / s_min above `max_cond` falls back to torch.linalg.svd; a random SPARC channel with
     n = 2N (cfg2, cfg4) sits near kappa = 6, a square one near N.  Returns (U, s, Vh) as torch.linalg.svd(A,
-    full_matrices=False): s descending, U [n, k], Vh [k, N], k = min(n, N)."""
+    full_matrices=False): s descending, U [n, k], Vh [k, N], k = min(n, N).
+    method='eigh' (default) is the path above.  method='jacobi' (a ROCm [n, N] or [G, n, N] complex64
+    tensor; a CPU tensor raises ValueError: there is no CPU fallback) takes the eigendecomposition
+    from the library's batched float64 Jacobi solver instead (amp_eigh_run, csrc/amp_eigh.hip), which
+    works on the channels of a stack side by side where rocSOLVER's eigh runs them one after
+    another: the smaller Gram matrix is formed in complex128 (one product per channel, in chunks of
+    channels whose complex128 copies stay under 1 GiB), s = sqrt(w) in float64, and the other factor
+    E^H A / s or A E / s is formed in COMPLEX128 as well, then everything is rounded to complex64 /
+    float32: the factors come out at float32 rounding level.  The float64 Gram matrix
+    keeps the small singular values the float32 one loses, so a larger max_cond may be passed with
+    it (the solver itself gives up where s_min / s_max < 2^-20).  A channel that did not converge is
+    redone by the eigh path, alone, with one RuntimeWarning per call; k above the solver's cap
+    (AMP_EIGH_MAX_K = 640) uses the eigh path.  Channel g of a stack gets the bits of the 2-D call on
+    A[g]."""
+    if method not in ('eigh', 'jacobi'):
+        raise ValueError(f"svd_gram: method must be 'eigh' or 'jacobi', got {method!r}")
+    if method == 'jacobi':
+        if A.device.type != 'cuda':
+            raise ValueError(f"svd_gram(method='jacobi') needs a ROCm device tensor (got {A.device}); there is "
+                             'no CPU fallback')
+        if A.dtype != torch.complex64 or A.dim() not in (2, 3):
+            raise ValueError(f"svd_gram(method='jacobi') takes a complex64 [n, N] or [G, n, N] tensor, got "
+                             f'{A.dtype} {tuple(A.shape)}')
+        out = _svd_jacobi(A if A.dim() == 3 else A.unsqueeze(0), max_cond)
+        if out is not None:
+            return out if A.dim() == 3 else tuple(f[0] for f in out)
     n, N = A.shape[-2], A.shape[-1]
     tall = n >= N
     G = A.mH @ A if tall else A @ A.mH
@@ -89,7 +186,8 @@ class Model(nn.Module):
     def __init__(self, config: Config, detector: str = 'vamp', path: str | None = None, amp=None,
                  seed: int | None = None, rng: str = 'host', group_epochs: bool = False,
                  shard: str = 'epochs', group_trials: int = 0, trial_channels: int = 0,
-                 trials_ws_limit: int = 4 << 30, synth_trials: bool = False) -> None:
+                 trials_ws_limit: int = 4 << 30, synth_trials: bool = False,
+                 device_svd: str = 'eigh') -> None:
         """rng='host' (default): the reference's numpy / torch-CPU random streams, bit for bit
         (parity mode).  rng='device': channel, messages and noise drawn on the GPU and the SVD
         on the GPU through the Gram matrix's eigendecomposition (svd_gram; throughput mode: same
@@ -125,6 +223,18 @@ class Model(nn.Module):
         id = (point index << 32) + epoch // res), so the sweep's Losses do not depend on
         group_trials / trial_channels; every call, a single trial included, goes through
         forward_trials.  The channels' transposes count towards trials_ws_limit.
+        device_svd (needs rng='device' and the VAMP detector, else ValueError): how svd_gram takes the
+        channels' SVDs in throughput mode: 'eigh' (default: torch.linalg.eigh, the channels of a stack one
+        after another) or 'jacobi' (opt-in: the library's batched float64 Jacobi solver, svd_gram(A,
+        method='jacobi'): the channels of a stack side by side; factors at float32 rounding level, other
+        phases and rounding than 'eigh', so the two settings' sweeps agree statistically, not bit for bit).
+        Measured on an MI355X at the published 528 x 2560 shape (profiles/svd_jacobi_bench.jsonl, DESIGN.md
+        §7), eigh / jacobi: 11.47 / 4.76 ms per channel with 10 channels per call, 11.43 / 3.21 with 84; VAMP
+        end to end 11.65 / 3.24 ms per trial at res = 1 and 1.200 / 0.521 at res = 10.  It is SLOWER where a
+        call holds a single channel: 11.95 / 25.65 ms for one channel alone (6.40 / 8.58 at cfg4's 512 x 256),
+        0.170 / 0.295 ms per trial at res = 100 with group_trials = 100; so it is for synth_trials sweeps
+        with several channels per call, not for the per-epoch loop.  TrialSynth's streams depend only on the seed, so a sweep
+        with either setting sees the same inputs.
         shard (with torch.distributed): 'epochs' (default) gives each rank whole epochs with its
         own random stream and merges the metrics once per SNR point; 'trials' (SURVEY §8(e)
         exact-compat, VAMP / BAMP / SCAMP) gives every rank the SAME epochs (one seed) and splits each batch's
@@ -154,6 +264,11 @@ class Model(nn.Module):
         self.amp = amp if amp is not None else _detector(detector, config, random_trials=rnd)
         self.loss = Loss(config)
         self.rng = rng
+        if device_svd not in ('eigh', 'jacobi'):
+            raise ValueError(f"device_svd must be 'eigh' or 'jacobi', got {device_svd!r}")
+        if device_svd != 'eigh' and (rng != 'device' or detector != 'vamp'):
+            raise ValueError("device_svd: the device-side SVD is taken for rng='device' and the VAMP detector only")
+        self.device_svd = device_svd
         self.channel = Channel(config, rng=rng)
         self.data = Data(config, rng=rng)
         self.path = path if path is not None else f'Simulations/{_DIRS[detector]}/{config.name}'
@@ -398,7 +513,7 @@ class Model(nn.Module):
                 _, W, A, At, svd = held
             else:
                 W, A, At = self.synth.channels(G, point + b0)
-                svd = svd_gram(A) if self.detector == 'vamp' else None
+                svd = self._svd_gram(A) if self.detector == 'vamp' else None
                 held = (b0, W, A, At, svd) if G == 1 else None
             x, sym, idx, y = self.synth.trials(At, E, res if G > 1 else E, SNR, point + e0)
             per = {'per_channel': res} if G > 1 else {}
@@ -407,6 +522,10 @@ class Model(nn.Module):
             else:
                 ch = ((W,) if self.detector == 'scamp' else ()) + ((A,) if G > 1 else (A[0],))
             yield from self.amp.forward_trials(*ch, y, SNR, x, sym, idx, **per)
+
+    def _svd_gram(self, A):
+        # the default keeps calling svd_gram(A) exactly as before (tools replace it by a one-argument function)
+        return svd_gram(A) if self.device_svd == 'eigh' else svd_gram(A, method=self.device_svd)
 
     def _per_epoch_channels(self) -> bool:
         """Whether one launch may hold epochs with different channels (VAMP.epochs_channels_eligible)."""
@@ -422,7 +541,7 @@ class Model(nn.Module):
             self._W = W
             if self.detector == 'vamp':
                 if self.rng == 'device':
-                    self._svd = svd_gram(A)
+                    self._svd = self._svd_gram(A)
                 else:   # LAPACK on the host, as the reference's CPU path (vamp_model.py:58)
                     U, s, Vh = torch.linalg.svd(A.cpu(), full_matrices=False)
                     self._svd = (U.to(A.device), s.to(A.device), Vh.to(A.device))

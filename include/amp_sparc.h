@@ -716,6 +716,40 @@ int amp_synth_channels(const amp_dims* d, const amp_synth_args* a, int32_t chann
 int amp_synth_trials(const amp_dims* d, const amp_constellation* c, const amp_synth_args* a, int32_t trials,
                      int32_t per_channel, void* stream);
 
+/* ---- Batched Hermitian eigensolver for stacks of Gram matrices — replaces torch.linalg.eigh inside
+ *      model.svd_gram, which stands in for the per-channel torch.linalg.svd of vamp_model.py:57-58.
+ *      A cyclic one-sided (Hestenes) Jacobi iteration in float64 on the columns of G: pair (p, q)
+ *      is rotated when |g_p^H g_q| > tol sqrt(|g_p|^2 |g_q|^2); once a whole sweep rotates nothing
+ *      the columns are orthogonal, their norms are the eigenvalues and the normalised columns the
+ *      eigenvectors.  Columns are paired by a round-robin over column blocks, one plain launch per
+ *      round, grid (block pairs) x batch; convergence is per matrix (a finished matrix is left
+ *      alone whatever the rest of the batch does, so matrix m of a batch gets the bits of a batch
+ *      of its own).  Unlike the other entry points this one MAY synchronise the stream: from the
+ *      ninth sweep on the host reads the sweep's rotation counts back to stop launching once every
+ *      matrix is done (never while the stream is being captured: a captured call launches every
+ *      sweep, and finished matrices' workgroups return at once).
+ *      Eigenvectors are defined for matrices whose smallest eigenvalue is above 2^-40 of the
+ *      largest; below that, and when max_sweeps sweeps did not suffice, converged is 0 (w and E
+ *      still hold finite values).  AMP_E_ARG with a message, before anything is launched: k outside
+ *      [1, AMP_EIGH_MAX_K], batch outside [1, 65535], null pointers, a short workspace, a negative
+ *      (or NaN) tol, max_sweeps outside [0, AMP_EIGH_MAX_SWEEPS]. */
+#define AMP_EIGH_MAX_K 640        /* every shape a persistent or trial engine takes; the published one has k = 528 */
+#define AMP_EIGH_MAX_SWEEPS 24
+typedef struct amp_eigh_args {
+    const void* G;        /* c128 [batch][k][k], Hermitian positive semidefinite (a Gram matrix); not written */
+    void* E;              /* out c128 [batch][k][k], row-major: column j is the unit eigenvector of w[j] */
+    void* w;              /* out f64 [batch][k], descending */
+    void* info;           /* out int32 [batch][2]: sweeps run (the closing one included), converged 0/1 */
+    void* workspace; size_t workspace_bytes;
+    double tol;           /* a pair is rotated when |g_p^H g_q| > tol sqrt(|g_p|^2 |g_q|^2); 0 means 1e-9 */
+    int32_t max_sweeps;   /* 0 means AMP_EIGH_MAX_SWEEPS (24) */
+} amp_eigh_args;
+size_t amp_eigh_workspace_bytes(int32_t k, int32_t batch);        /* 0 where the run would refuse */
+int amp_eigh_run(const amp_eigh_args* a, int32_t k, int32_t batch, void* stream);
+/* Measurement switch (tools/svd_jacobi_bench.py; process-wide, as amp_debug_persist_timing): on = 0
+ * launches every sweep without the host's look at the counts, on != 0 (the default) restores it. */
+int amp_eigh_debug_readback(int32_t on);
+
 /* ---- Element-wise shrinkage denoisers — replace Shrink (shrink.py:8-166).
  * r: [count] complex64 (is_complex != 0) or float32; cov: cov_vec [count] float32, or
  * cov_scalar when cov_vec is NULL (a 0-dim tensor in the reference).

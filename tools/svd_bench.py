@@ -5,15 +5,23 @@ new channel) on the GPU, cfg4 shape (A: 512 x 256 complex64), by method:
   svdK      torch.linalg.svd of K channels stacked (one batched call)
   gramK     the Hermitian eigendecomposition of the K Gram matrices A^H A (torch.linalg.eigh,
             batched): Vh = eigenvectors^H, s = sqrt(eigenvalues) (descending), U = A V / s
+  jacobiK   model.svd_gram(A, method='jacobi') on the K channels: the library's batched float64 Jacobi
+            eigensolver (amp_eigh_run) on the Gram matrices, factors rounded to complex64
 Prints ms per channel and the reconstruction / orthogonality error of each.
 
   python tools/svd_bench.py [--n 512] [--N 256] [--K 1,8,32]
 """
 import argparse
 import json
+import os
+import sys
 import time
 
 import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, 'amp-sparc-spatialmodulation_amd')]
+from model import svd_gram  # noqa: E402
 
 
 def gram_svd(A):
@@ -48,7 +56,8 @@ def main():
     for K in [int(k) for k in a.K.split(',')]:
         A = (torch.randn(K, a.n, a.N, 2, device=dev, generator=g) / (2 * a.n) ** 0.5)
         A = torch.view_as_complex(A.contiguous())
-        for name, fn in (('svd', lambda X: torch.linalg.svd(X, full_matrices=False)), ('gram', gram_svd)):
+        for name, fn in (('svd', lambda X: torch.linalg.svd(X, full_matrices=False)), ('gram', gram_svd),
+                         ('jacobi', lambda X: svd_gram(X, method='jacobi'))):
             fn(A)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
